@@ -10,6 +10,12 @@ outputs are all-gathered over RCCL at the end of the step (weak scaling).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--timesteps T] [--dtype bf16]
     python bench.py --workload diffwave|wavegrad     # BASELINE configs #3 / #4 (not the headline)
+    python bench.py --full                           # the headline plus everything described below
+    python bench.py --dump-outputs DIR               # DIR/out.npy: the last timed step's samples
+
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and
+prints the result line (`roofline` of the UNet line, `cpu_baseline` and `variants` are then absent
+or null).  Everything else runs only with --full, after the timed region:
 
 At N=1 the headline line also carries `variants`: the fp32 parity path (2 timed runs) and the other
 16-bit type (fp16 beside the bf16 headline, 5 timed runs), timed in the same process on the same
@@ -21,6 +27,11 @@ the most time in a sampling run): algorithmic bytes per launch over its average 
 events around every launch of one extra (untimed) sampling run, with the whole reverse step
 reported beside it; `cpu_baseline` times a PyTorch-CPU restatement of the reference
 (oracle/unet_torch.py) at the config's batch on this host's cores.
+
+--dump-outputs DIR writes what the last timed step returned (the denoised batch a caller of
+sharded_infer receives, [B, 1, N] for the UNet; inputs, weights and noise are seeded, so two
+builds can be compared output for output) as float32 DIR/out.npy; above 64 MB a fixed seeded
+sample of its elements is written.
 """
 import argparse
 import json
@@ -134,6 +145,22 @@ def init_ranks():
 def log(msg):
     """progress on stderr (the JSON line stays the only stdout output)"""
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: the last timed step's samples as float32 `path`/out.npy.  An output above
+    DUMP_MAX_BYTES is cut to a fixed sample of its flattened elements (seeded, sorted indices)."""
+    import numpy as np
+    a = out.detach().float().cpu().numpy()
+    if a.nbytes > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_BYTES // 4, replace=False))
+        a = a.reshape(-1)[idx]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "out.npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log(f"wrote {os.path.join(path, 'out.npy')} {a.shape}")
 
 
 def kernel_src_hash():
@@ -369,6 +396,8 @@ def main_spec(args):
         elapsed = float(tt.item())
     if not torch.isfinite(result["out"]).all():
         raise RuntimeError("non-finite samples")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, result["out"])
     if rank == 0:
         es = 2 if args.dtype != "f32" else 4
         tfs = args.steps * T * B * W["gflop"] / elapsed / 1e3      # whole-job MFMA rate per GPU
@@ -426,8 +455,15 @@ def main():
     ap.add_argument("--workload", default="unet", choices=["unet", "diffwave", "wavegrad"])
     ap.add_argument("--num-samples", type=int, default=None,
                     help="UNet chunk length (config #5: 32832 = 512 frames); default config_unet.json's 16448")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline profile, the fp16 / fp32 sub-records and "
+                         "the CPU baseline (each can be dropped again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output as DIR/out.npy (float32)")
     import sys as _sys
     args = ap.parse_args()
+    if not args.full:                                               # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_profile = args.no_variants = True
     args.batch_set = any(a.startswith("--batch") for a in _sys.argv[1:])
     args.timesteps_set = any(a.startswith("--timesteps") for a in _sys.argv[1:])
     if args.workload != "unet":
@@ -487,6 +523,8 @@ def main():
         elapsed = float(tt.item())
     if not torch.isfinite(result["out"]).all():
         raise RuntimeError("non-finite samples")
+    if rank == 0 and args.dump_outputs:                             # before the sub-records reuse `result`
+        dump_outputs(args.dump_outputs, result["out"])
 
     roofline = None
     log(f"timed region: {elapsed:.2f} s")

