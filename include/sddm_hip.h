@@ -59,7 +59,11 @@ void sddm_destroy(sddm_ctx* ctx);
 /* Replaces config.init_obj('diffusion'|'network'|'arch', ...) (infer.py:37-39,
  * parse_config.py:82-95).  `json` is {"arch": {...}, "diffusion": {...}, "network": {...},
  * "num_samples": N} with the reference's type names and args verbatim
- * (config_unet.json, config_diffwave.json, config_wavegrad.json). */
+ * (config_unet.json, config_diffwave.json, config_wavegrad.json, and the default config.json).
+ * Network types: UNetModified2, DenoiseWaveGrad1 and DenoiseWaveGrad3 under arch SDDM (with its
+ * p_transition / noise_condition args); DiffWave and WaveGrad under arch SDDM_spectrogram.  Any
+ * other pairing or type (DenoiseWaveGrad2 among them) returns SDDM_ERR_NOT_IMPLEMENTED.  The 1-D
+ * networks need no num_samples: they take any positive multiple of their hop (see sddm_sample). */
 int sddm_configure(sddm_ctx* ctx, const char* json);
 
 /* Replaces model.load_state_dict(state_dict) (infer.py:51) one tensor at a time.  `key` is
@@ -76,7 +80,10 @@ int sddm_missing_params(sddm_ctx* ctx, int64_t* n_missing);
  * when the arch is SDDM_spectrogram, then `cond` is the spectrogram [B, bins, frames]).
  * cond: [B, 1, N] fp32 device; out: [B, 1, N] fp32 device (x_0).  Noise is the counter-based
  * stream keyed by (seed, draw, (row_offset + b) * N + n) so a row block sampled on any rank
- * equals the same rows of a single-device run. */
+ * equals the same rows of a single-device run.
+ * Geometry: UNetModified2 N = num_samples; DiffWave N = 256 frames; WaveGrad N = 300 frames;
+ * DenoiseWaveGrad1 N a positive multiple of 400 (2*2*4*5*5); DenoiseWaveGrad3 of 300 (2*2*3*5*5).
+ * Anything else returns SDDM_ERR_SHAPE before any launch. */
 int sddm_sample(sddm_ctx* ctx, const float* cond, int64_t B, int64_t N, uint64_t seed,
                 int64_t row_offset, float* out, void* stream);
 
@@ -96,7 +103,9 @@ int sddm_sample_continuous(sddm_ctx* ctx, const float* cond, int64_t B, int64_t 
                            int64_t row_offset, float* out, float* record, int sample_inter, void* stream);
 
 /* Replaces one noise_estimate_model(condition, x_t, noise_level) call (model.py:110):
- * noise_level: [B] fp32 device.  eps_out: [B, 1, N] fp32 device. */
+ * noise_level: [B] fp32 device.  eps_out: [B, 1, N] fp32 device.  cond is [B, 1, N] for
+ * UNetModified2, DenoiseWaveGrad1 and DenoiseWaveGrad3 (the noisy waveform; N as in sddm_sample)
+ * and the spectrogram [B, bins, frames] for DiffWave and WaveGrad. */
 int sddm_network_forward(sddm_ctx* ctx, const float* cond, const float* x_t,
                          const float* noise_level, int64_t B, int64_t N, float* eps_out,
                          void* stream);

@@ -1293,22 +1293,30 @@ int sddm_configure(sddm_ctx* c, const char* json) {
     c->configured = true;
     return SDDM_OK;
   }
-  if (c->net_type == "WaveGrad") {                               // wavegrad.py:140-179
-    if (c->arch_type != "SDDM_spectrogram") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "WaveGrad needs arch SDDM_spectrogram");
-    if (c->hop_samples != WGState::kHop)
-      FAIL(SDDM_ERR_NOT_IMPLEMENTED, "hop_samples %d: WaveGrad upsamples x300 (config_wavegrad.json:8)", c->hop_samples);
+  if (const wg::Variant* wv = wg::find_variant(c->net_type)) {   // wavegrad.py:140-179, 184-242, 307-353
+    if (wv->kind == wg::kWaveGrad) {
+      if (c->arch_type != "SDDM_spectrogram") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "WaveGrad needs arch SDDM_spectrogram");
+      if (c->hop_samples != wv->hop)
+        FAIL(SDDM_ERR_NOT_IMPLEMENTED, "hop_samples %d: WaveGrad upsamples x300 (config_wavegrad.json:8)", c->hop_samples);
+    } else {                                                     // waveform-conditioned: SDDM.infer (model.py:50-124)
+      if (c->arch_type != "SDDM") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "%s needs arch SDDM (its condition is a waveform)", wv->name);
+      c->hop_samples = wv->hop;
+    }
     c->T = T;
     c->tables.swap(tabs);
     c->tables_dirty = true;
     c->num_samples = -1;
     c->params.clear();
-    for (const auto& kv : wg_param_shapes()) {
+    auto ws = std::make_shared<WGState>();
+    ws->v = wv;
+    ws->shapes = wg_param_shapes(*wv);
+    for (const auto& kv : ws->shapes) {
       Param p;
       p.shape = kv.second;
       c->params[kv.first] = p;
     }
     c->dws.reset();
-    c->wgs = std::make_shared<WGState>();
+    c->wgs = ws;
     c->params_dirty = true;
     c->plan_B = -1;
     c->lanes.clear();

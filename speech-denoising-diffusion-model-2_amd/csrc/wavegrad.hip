@@ -1,4 +1,6 @@
-// WaveGrad denoiser (reference model/wavegrad.py) for SDDM_spectrogram.infer (model.py:212-257).
+// WaveGrad denoiser (reference model/wavegrad.py) for SDDM_spectrogram.infer (model.py:212-257), and
+// its waveform-conditioned variants DenoiseWaveGrad1 / DenoiseWaveGrad3 for SDDM.infer: the kernels
+// are generic in resample factor, channel count and length (wg_runtime.h holds the networks' tables).
 //
 // Activations are sample-major [B][T][C] in the compute dtype, so one time position's channels
 // are contiguous and each MFMA operand fragment (8 channels) is one 16-byte (bf16/f16) or two
@@ -588,6 +590,59 @@ hipError_t launch_wg_first(int dtype, const WGFirstArgs& a, hipStream_t s) {
   if (dtype == DT_F32) hipLaunchKernelGGL(wg_first_kernel<float>, grid, dim3(256), 0, s, a);
   else if (dtype == DT_BF16) hipLaunchKernelGGL(wg_first_kernel<bf16_t>, grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(wg_first_kernel<f16_t>, grid, dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// ---------------- DenoiseWaveGrad3 downsample.0: Conv1d(2, 32, 5, padding=2) on cat([y_t, x]) ----------------
+// One thread per position reads the 5-tap windows of both fp32 sources (channel 0 = y_t, channel 1
+// = x, wavegrad.py:343) and writes the position's 32 channels as 8 four-channel vector stores
+template <typename T>
+__global__ __launch_bounds__(256) void wg_first2_kernel(WGFirst2Args a) {
+  __shared__ float w[32 * 2 * 5], bias[32];
+  const int tid = threadIdx.x;
+  if (a.t_dev && blockIdx.x == 0 && tid == 0) *a.t_dev -= 1;   // this step's t
+  for (int i = tid; i < 320; i += 256) w[i] = a.w[i];
+  if (tid < 32) bias[tid] = a.b[tid];
+  __syncthreads();
+  const int64_t total = (int64_t)a.B * a.N;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < total; i += (int64_t)gridDim.x * 256) {
+    const int n = (int)(i % a.N);
+    const float* y = a.y_t + (i - n);
+    const float* x = a.x + (i - n);
+    float yv[5], xv[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      const int m = n + k - 2;
+      const bool in = m >= 0 && m < a.N;
+      yv[k] = in ? y[m] : 0.f;
+      xv[k] = in ? x[m] : 0.f;
+    }
+    T* o = (T*)a.out + i * 32;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      float v[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int co = q * 4 + e;
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) s += w[co * 10 + k] * yv[k];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) s += w[co * 10 + 5 + k] * xv[k];
+        v[e] = s + bias[co];
+      }
+      store4<T>(o + q * 4, v[0], v[1], v[2], v[3]);
+    }
+  }
+}
+
+hipError_t launch_wg_first2(int dtype, const WGFirst2Args& a, hipStream_t s) {
+  if (!a.y_t || !a.x || !a.w || !a.b || !a.out || a.B < 1 || a.N < 1) return hipErrorInvalidValue;
+  const int64_t total = (int64_t)a.B * a.N;
+  const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 16384)));
+  if (dtype == DT_F32) hipLaunchKernelGGL(wg_first2_kernel<float>, grid, dim3(256), 0, s, a);
+  else if (dtype == DT_BF16) hipLaunchKernelGGL(wg_first2_kernel<bf16_t>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(wg_first2_kernel<f16_t>, grid, dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -38,6 +38,12 @@ bool wg_conv_uses_lds(const WGConvArgs& a);
 struct WGFirstArgs { const float* audio; const float* w; const float* b; void* out; int B, N; int* t_dev; };
 hipError_t launch_wg_first(int dtype, const WGFirstArgs& a, hipStream_t s);
 
+// DenoiseWaveGrad3's downsample.0: Conv1d(2, 32, 5, padding=2) over cat([y_t, x], dim=1) (wavegrad.py:316,
+// 343) read from its two fp32 sources [B][N] (channel 0 = y_t, channel 1 = x; no concatenated buffer)
+// -> [B][N][32] (T); w [32][2][5], b [32] fp32; decrements the device step counter like launch_wg_first
+struct WGFirst2Args { const float* y_t; const float* x; const float* w; const float* b; void* out; int B, N; int* t_dev; };
+hipError_t launch_wg_first2(int dtype, const WGFirst2Args& a, hipStream_t s);
+
 // FiLM modulation materialised once per element: u[b][t][c] = leaky_relu(0.2)(shift + scale * x)
 // (wavegrad.py:98-99, 104-105, 107-108); film [B][T][2C] (shift | scale), x / u [B][T][C]
 struct WGFilmArgs { const void* x; const void* film; void* out; int64_t BT; int C; };

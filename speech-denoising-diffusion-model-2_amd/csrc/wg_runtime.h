@@ -1,23 +1,80 @@
-// WaveGrad path of the runtime (included by sddm_runtime.cpp after sddm_ctx): configuration,
-// weight packing, workspace and the SDDM_spectrogram.infer loop (reference model/model.py:212-257,
-// model/wavegrad.py).  Kernels: wavegrad.hip.
+// WaveGrad-family path of the runtime (included by sddm_runtime.cpp after sddm_ctx): configuration,
+// weight packing, workspace and the sampling loops of three networks of reference model/wavegrad.py,
+// described by one table each (wg::Variant) and run by the same kernels (wavegrad.hip):
 //
-// The reference wiring of SDDM_spectrogram + WaveGrad fails (x_t [B,1,N] reaches a
-// Conv1d as 4-D, and the squeezed [B,N] output broadcasts against x_t); the library applies the
-// adapter: audio = x_t[:, 0], noise level [B], eps -> [B,1,N].
+//   WaveGrad          (wavegrad.py:140-179) under SDDM_spectrogram.infer (model.py:212-257)
+//   DenoiseWaveGrad1  (wavegrad.py:184-242) under SDDM.infer (model.py:50-124), waveform condition
+//   DenoiseWaveGrad3  (wavegrad.py:307-353) under SDDM.infer, waveform condition
 //
+// WaveGrad.  The reference wiring of SDDM_spectrogram + WaveGrad fails (x_t [B,1,N]
+// reaches a Conv1d as 4-D, and the squeezed [B,N] output broadcasts against x_t); the library
+// applies the adapter: audio = x_t[:, 0], noise level [B], eps -> [B,1,N].
 // Step-invariant per sampling call (the spectrogram does not change across steps): the spectrogram
 // transpose, first_conv, and upsample.0's block1 and block2[0] (no FiLM reaches them).  The
 // PositionalEncoding rows of all t are one launch.  Per reverse step: downsample.0, 5 FiLMs
 // (2 convs each), 4 DBlocks (4 convs), upsample.0 (3 convs), upsample.1-4 (5 convs), last_conv,
 // transition -- 52 launches.
+//
+// DenoiseWaveGrad1.  The condition is constant across steps, so the whole downsample_x encoder
+// (stem + 5 DBlocks, 21 launches) and upsample.0's block1 / block2[0] run once per sampling call;
+// the per-step launches are WaveGrad's 52 (y_t branch, FiLMs, the rest of the UBlocks, last_conv,
+// transition).
+//
+// DenoiseWaveGrad3.  cat([y_t, x]) feeds downsample.0, so nothing hoists: per step the two-source
+// stem, 4 DBlocks, 5 FiLMs, the bottleneck DBlock (4 convs), all five UBlocks in full (5 convs
+// each), last_conv, transition -- 58 launches.
 #pragma once
 #include "wg_kernels.h"
 
+namespace wg {
+struct Down { int ci, co, f; };
+struct Film { int ci, co; };
+struct Up { int ci, h, f; int dil[4]; };
+enum { kWaveGrad = 0, kDenoise1 = 1, kDenoise3 = 2 };
+// One network of the family.  `bottom` is the extra DBlock whose output feeds upsample.0
+// (downsample_x.5 of DenoiseWaveGrad1, bottleneck of DenoiseWaveGrad3; f = 0: none, WaveGrad's
+// upsample.0 reads first_conv(spectrogram)).  `hoist`: upsample.0's input does not depend on the
+// step, so it and upsample.0's block1 / block2[0] are computed once per sampling call.
+struct Variant {
+  int kind; const char* name; int hop; int stem_ci;
+  Down down[5]; Film film[5]; Up up[5];
+  int enc_off[5]; int enc_n;
+  Down bottom; const char* bottom_key; bool hoist;
+};
+static const Variant kVariants[3] = {
+    {kWaveGrad, "WaveGrad", 300, 1,                                                                 // 5 * 5 * 3 * 2 * 2
+     {{1, 32, 1}, {32, 128, 2}, {128, 128, 2}, {128, 256, 3}, {256, 512, 5}},                        // wavegrad.py:143-149
+     {{32, 128}, {128, 128}, {128, 256}, {256, 512}, {512, 512}},                                    // wavegrad.py:150-156
+     {{768, 512, 5, {1, 2, 1, 2}}, {512, 512, 5, {1, 2, 1, 2}}, {512, 256, 3, {1, 2, 4, 8}},
+      {256, 128, 2, {1, 2, 4, 8}}, {128, 128, 2, {1, 2, 4, 8}}},                                     // wavegrad.py:157-163
+     {0, 32, 160, 288, 544}, 1056,                                                                   // 32 + 128 + 128 + 256 + 512
+     {0, 0, 0}, "", true},
+    {kDenoise1, "DenoiseWaveGrad1", 400, 1,                                                         // 5 * 5 * 4 * 2 * 2
+     {{1, 32, 1}, {32, 128, 2}, {128, 128, 2}, {128, 256, 4}, {256, 512, 5}},                        // wavegrad.py:191-198
+     {{32, 128}, {128, 128}, {128, 256}, {256, 512}, {512, 512}},                                    // wavegrad.py:210-216
+     {{512, 512, 5, {1, 2, 1, 2}}, {512, 512, 5, {1, 2, 1, 2}}, {512, 256, 4, {1, 2, 4, 8}},
+      {256, 128, 2, {1, 2, 4, 8}}, {128, 128, 2, {1, 2, 4, 8}}},                                     // wavegrad.py:217-223
+     {0, 32, 160, 288, 544}, 1056,
+     {512, 512, 5}, "downsample_x.5.", true},                                                        // wavegrad.py:207
+    {kDenoise3, "DenoiseWaveGrad3", 300, 2,                                                         // 5 * 5 * 3 * 2 * 2
+     {{2, 32, 1}, {32, 128, 2}, {128, 128, 2}, {128, 256, 3}, {256, 512, 5}},                        // wavegrad.py:314-321
+     {{32, 128}, {128, 128}, {128, 256}, {256, 512}, {512, 512}},                                    // wavegrad.py:325-331
+     {{512, 512, 5, {1, 2, 1, 2}}, {512, 512, 5, {1, 2, 1, 2}}, {512, 256, 3, {1, 2, 4, 8}},
+      {256, 128, 2, {1, 2, 4, 8}}, {128, 128, 2, {1, 2, 4, 8}}},                                     // wavegrad.py:332-338
+     {0, 32, 160, 288, 544}, 1056,
+     {512, 512, 5}, "bottleneck.", false},                                                           // wavegrad.py:323
+};
+static const Variant* find_variant(const std::string& name) {
+  for (const Variant& v : kVariants)
+    if (name == v.name) return &v;
+  return nullptr;
+}
+}  // namespace wg
+
 struct WGState {
-  static constexpr int kHop = 300;                    // 5 * 5 * 3 * 2 * 2
-  static constexpr int kSpecC = 128;
-  static constexpr int kEncN = 1056;                  // 32 + 128 + 128 + 256 + 512
+  static constexpr int kSpecC = 128;                  // WaveGrad's first_conv input channels
+  const wg::Variant* v = &wg::kVariants[0];           // the context's network (set by sddm_configure)
+  std::map<std::string, std::vector<int64_t>> shapes; // its state-dict shapes (wg_param_shapes)
   std::map<std::string, size_t> woff;                 // packed weights in ctx->warena
   size_t off_tables = 0, off_sp = 0, off_enctab = 0, off_ev = 0;
   Arena act;                                          // activations of the current (B, F)
@@ -25,40 +82,34 @@ struct WGState {
   int B = -1, F = -1;
 };
 
-namespace wg {
-struct Down { int ci, co, f; };
-struct Film { int ci, co; };
-struct Up { int ci, h, f; int dil[4]; };
-static const Down kDown[5] = {{1, 32, 1}, {32, 128, 2}, {128, 128, 2}, {128, 256, 3}, {256, 512, 5}};  // wavegrad.py:143-149
-static const Film kFilm[5] = {{32, 128}, {128, 128}, {128, 256}, {256, 512}, {512, 512}};           // wavegrad.py:150-156
-static const Up kUp[5] = {{768, 512, 5, {1, 2, 1, 2}}, {512, 512, 5, {1, 2, 1, 2}}, {512, 256, 3, {1, 2, 4, 8}},
-                          {256, 128, 2, {1, 2, 4, 8}}, {128, 128, 2, {1, 2, 4, 8}}};                  // wavegrad.py:157-163
-static const int kEncOff[5] = {0, 32, 160, 288, 544};
-}  // namespace wg
-
-// state-dict shapes of WaveGrad (wavegrad.py:140-165) without the noise_estimate_model. prefix
-static std::map<std::string, std::vector<int64_t>> wg_param_shapes() {
+// state-dict shapes of a variant (wavegrad.py:140-165, 189-224, 312-339) without the
+// noise_estimate_model. prefix
+static std::map<std::string, std::vector<int64_t>> wg_param_shapes(const wg::Variant& v) {
   std::map<std::string, std::vector<int64_t>> s;
   auto conv = [&](const std::string& p, int co, int ci, int k) {
     s[p + ".weight"] = {co, ci, k};
     s[p + ".bias"] = {co};
   };
-  conv("downsample.0", 32, 1, 5);
-  for (int i = 1; i < 5; ++i) {
-    const wg::Down& d = wg::kDown[i];
-    const std::string p = "downsample." + std::to_string(i) + ".";
+  auto dblock = [&](const std::string& p, const wg::Down& d) {
     conv(p + "residual_dense", d.co, d.ci, 1);
     conv(p + "conv.0", d.co, d.ci, 3);
     conv(p + "conv.1", d.co, d.co, 3);
     conv(p + "conv.2", d.co, d.co, 3);
+  };
+  conv("downsample.0", 32, v.stem_ci, 5);
+  for (int i = 1; i < 5; ++i) dblock("downsample." + std::to_string(i) + ".", v.down[i]);
+  if (v.kind == wg::kDenoise1) {                     // downsample_x: the same ladder plus the bottom DBlock
+    conv("downsample_x.0", 32, 1, 5);
+    for (int i = 1; i < 5; ++i) dblock("downsample_x." + std::to_string(i) + ".", v.down[i]);
   }
+  if (v.bottom.f) dblock(v.bottom_key, v.bottom);
   for (int i = 0; i < 5; ++i) {
     const std::string p = "film." + std::to_string(i) + ".";
-    conv(p + "input_conv", wg::kFilm[i].ci, wg::kFilm[i].ci, 3);
-    conv(p + "output_conv", 2 * wg::kFilm[i].co, wg::kFilm[i].ci, 3);
+    conv(p + "input_conv", v.film[i].ci, v.film[i].ci, 3);
+    conv(p + "output_conv", 2 * v.film[i].co, v.film[i].ci, 3);
   }
   for (int i = 0; i < 5; ++i) {
-    const wg::Up& u = wg::kUp[i];
+    const wg::Up& u = v.up[i];
     const std::string p = "upsample." + std::to_string(i) + ".";
     conv(p + "block1", u.h, u.ci, 1);
     conv(p + "block2.0", u.h, u.ci, 3);
@@ -66,8 +117,8 @@ static std::map<std::string, std::vector<int64_t>> wg_param_shapes() {
     conv(p + "block3.0", u.h, u.h, 3);
     conv(p + "block3.1", u.h, u.h, 3);
   }
-  conv("first_conv", 768, 128, 3);
-  conv("last_conv", 1, 128, 3);
+  if (v.kind == wg::kWaveGrad) conv("first_conv", v.up[0].ci, WGState::kSpecC, 3);
+  conv("last_conv", 1, v.up[4].h, 3);
   return s;
 }
 
@@ -89,14 +140,15 @@ static int wg_upload_weights(sddm_ctx* c) {
     blobs.push_back(std::move(b));
   };
   // Conv1d weight [Cout][Cin][K] -> [Cout_pad64][K][Cin] in the compute dtype (zero pad rows)
-  for (const auto& kv : wg_param_shapes()) {
+  const wg::Variant& v = *d.v;
+  for (const auto& kv : d.shapes) {
     const std::string& key = kv.first;
     if (key.size() < 7 || key.compare(key.size() - 7, 7, ".weight")) continue;
     const std::string base = key.substr(0, key.size() - 7);
     const std::vector<float>& w = c->params.at(key).data;
     const int co = (int)kv.second[0], ci = (int)kv.second[1], k = (int)kv.second[2];
     add_f32(base + ".b", c->params.at(base + ".bias").data);
-    if (base == "downsample.0") { add_f32(base + ".w", w); continue; }   // fp32 [32][1][5], VALU kernel
+    if (base == "downsample.0" || base == "downsample_x.0") { add_f32(base + ".w", w); continue; }   // fp32 [32][1 | 2][5], VALU kernels
     const int cop = (co + 63) / 64 * 64;
     Blob b;
     b.bytes.assign((size_t)cop * k * ci * es, 0);
@@ -110,7 +162,7 @@ static int wg_upload_weights(sddm_ctx* c) {
   {  // PositionalEncoding exp vectors, torch fp32 op order (wavegrad.py:45-47)
     std::vector<float> ev;
     for (int i = 0; i < 5; ++i) {
-      const int cnt = wg::kFilm[i].ci / 2;
+      const int cnt = v.film[i].ci / 2;
       for (int k = 0; k < cnt; ++k) {
         const float step = (float)k / (float)cnt;
         ev.push_back(std::exp((float)(-std::log(1e4)) * step));
@@ -120,7 +172,7 @@ static int wg_upload_weights(sddm_ctx* c) {
   }
   d.off_tables = A.reserve(sizeof(float) * 14 * (c->T + 1));
   d.off_sp = A.reserve(64);
-  d.off_enctab = A.reserve(sizeof(float) * (size_t)(c->T + 1) * WGState::kEncN);
+  d.off_enctab = A.reserve(sizeof(float) * (size_t)(c->T + 1) * v.enc_n);
   c->off_tables = d.off_tables;
   SDDM_HIP_CHECK(A.commit());
   for (const auto& b : blobs) SDDM_HIP_CHECK(hipMemcpy(A.base + b.off, b.bytes.data(), b.bytes.size(), hipMemcpyHostToDevice));
@@ -128,6 +180,13 @@ static int wg_upload_weights(sddm_ctx* c) {
   c->tables_dirty = true;
   d.B = -1;
   return SDDM_OK;
+}
+
+// lengths of the levels for F bottom positions: L[0] = hop F samples .. L[4]; L[5] = F (upsample.0's input)
+static void wg_lengths(const wg::Variant& v, int F, int64_t* L) {
+  L[0] = (int64_t)v.hop * F;
+  for (int i = 1; i < 5; ++i) L[i] = L[i - 1] / v.down[i].f;
+  L[5] = F;
 }
 
 // activation buffers for (B, F): name -> [B][len][C] in the compute dtype
@@ -139,27 +198,27 @@ static int wg_prepare(sddm_ctx* c, int B, int F) {
   A.reset();
   d.aoff.clear();
   auto buf = [&](const std::string& n, int64_t len, int C) { d.aoff[n] = A.reserve(es * (size_t)B * len * C); };
+  const wg::Variant& v = *d.v;
   int64_t L[6];
-  L[0] = (int64_t)WGState::kHop * F;
-  for (int i = 1; i < 5; ++i) L[i] = L[i - 1] / wg::kDown[i].f;
-  L[5] = F;
+  wg_lengths(v, F, L);
   buf("d0", L[0], 32);
   for (int i = 0; i < 5; ++i) {
     const std::string s = std::to_string(i);
-    if (i > 0) for (const char* n : {"r", "a", "b", ""}) buf("d" + s + n, L[i], wg::kDown[i].co);
-    buf("f" + s + "a", L[i], wg::kFilm[i].ci);
-    buf("f" + s, L[i], 2 * wg::kFilm[i].co);
+    if (i > 0) for (const char* n : {"r", "a", "b", ""}) buf("d" + s + n, L[i], v.down[i].co);
+    buf("f" + s + "a", L[i], v.film[i].ci);
+    buf("f" + s, L[i], 2 * v.film[i].co);
   }
-  buf("spec", L[5], WGState::kSpecC);
-  buf("uin", L[5], 768);
+  if (v.kind == wg::kWaveGrad) buf("spec", L[5], WGState::kSpecC);
+  if (v.bottom.f) for (const char* n : {"r", "a", "b"}) buf(std::string("bn") + n, L[5], v.bottom.co);   // bottom DBlock scratch
+  buf("uin", L[5], v.up[0].ci);
   for (int i = 0; i < 5; ++i) {
     const std::string s = std::to_string(i);
     const int64_t lin = L[5 - i], lout = L[4 - i];
-    buf("u" + s + "b1", lin, wg::kUp[i].h);
-    for (const char* n : {"y0", "x", "z", "", "m", "p"}) buf("u" + s + n, lout, wg::kUp[i].h);   // m: leaky(film(x)); p: pre-2 fallback scratch
+    buf("u" + s + "b1", lin, v.up[i].h);
+    for (const char* n : {"y0", "x", "z", "", "m", "p"}) buf("u" + s + n, lout, v.up[i].h);   // m: leaky(film(x)); p: pre-2 fallback scratch
   }
   d.aoff["eps"] = A.reserve(sizeof(float) * (size_t)B * L[0]);
-  d.aoff["encb"] = A.reserve(sizeof(float) * (size_t)B * WGState::kEncN);
+  d.aoff["encb"] = A.reserve(sizeof(float) * (size_t)B * v.enc_n);
   SDDM_HIP_CHECK(A.commit());
   d.B = B;
   d.F = F;
@@ -195,7 +254,7 @@ static int wg_conv(sddm_ctx* c, WGConvSpec q, int B, const float* enc, int enc_p
   a.Tc = (int)q.Tc; a.Cin = q.Cin; a.K = q.K; a.dil = q.dil; a.pre = q.pre;
   a.film = q.film ? d.act.base + d.aoff.at(q.film) : nullptr;
   a.w = W.base + d.woff.at(q.w + ".w"); a.bias = W.at<float>(d.woff.at(q.w + ".b")); a.Cout = q.Cout;
-  a.post = q.post; a.enc = enc; a.enc_stride = WGState::kEncN; a.enc_off = q.enc_off; a.enc_per_b = enc_per_b;
+  a.post = q.post; a.enc = enc; a.enc_stride = d.v->enc_n; a.enc_off = q.enc_off; a.enc_per_b = enc_per_b;
   a.t_dev = t_dev;
   a.res = q.res ? d.act.base + d.aoff.at(q.res) : nullptr; a.res_map = q.res_map; a.res_f = q.res_f;
   a.res_T = (int)q.res_T;
@@ -211,66 +270,101 @@ static int wg_conv(sddm_ctx* c, WGConvSpec q, int B, const float* enc, int enc_p
 
 #define WG_TRY(x) do { const int _r = (x); if (_r) return _r; } while (0)
 
-static void wg_lengths(int F, int64_t* L) {
-  L[0] = (int64_t)WGState::kHop * F;
-  for (int i = 1; i < 5; ++i) L[i] = L[i - 1] / wg::kDown[i].f;
-  L[5] = F;
+// DBlock (wavegrad.py:126-137): weights p + {residual_dense, conv.0-2}, input xs [B][lin][dn.ci] ->
+// out [B][lout][dn.co]; scratch buffers o + {r, a, b}
+static int wg_dblock(sddm_ctx* c, const std::string& p, const char* xs, int64_t lin, const wg::Down& dn, int64_t lout,
+                     const std::string& o, const char* out, int B, hipStream_t s) {
+  WG_TRY(wg_conv(c, {xs, lin, dn.ci, WG_MAP_DOWN, dn.f, lout, dn.ci, p + "residual_dense", dn.co, 1, 1, 0, nullptr, 0, 0,
+                     nullptr, 0, 1, 0, (o + "r").c_str()}, B, nullptr, 0, nullptr, s));
+  WG_TRY(wg_conv(c, {xs, lin, dn.ci, WG_MAP_DOWN, dn.f, lout, dn.ci, p + "conv.0", dn.co, 3, 1, 1, nullptr, 0, 0,
+                     nullptr, 0, 1, 0, (o + "a").c_str()}, B, nullptr, 0, nullptr, s));
+  WG_TRY(wg_conv(c, {(o + "a").c_str(), lout, dn.co, WG_MAP_ID, 1, lout, dn.co, p + "conv.1", dn.co, 3, 2, 1, nullptr, 0, 0,
+                     nullptr, 0, 1, 0, (o + "b").c_str()}, B, nullptr, 0, nullptr, s));
+  WG_TRY(wg_conv(c, {(o + "b").c_str(), lout, dn.co, WG_MAP_ID, 1, lout, dn.co, p + "conv.2", dn.co, 3, 4, 1, nullptr, 0, 0,
+                     (o + "r").c_str(), WG_MAP_ID, 1, lout, out}, B, nullptr, 0, nullptr, s));
+  return SDDM_OK;
 }
 
-// step-invariant work of one call (wavegrad.py:175-177 for upsample.0's block1 / block2[0])
-static int wg_condition(sddm_ctx* c, const float* spec, int B, int F, hipStream_t s) {
-  WGState& d = *c->wgs;
-  int64_t L[6];
-  wg_lengths(F, L);
-  WGSpecArgs sa{spec, d.act.base + d.aoff.at("spec"), B, WGState::kSpecC, F};
-  SDDM_HIP_CHECK(launch_wg_spec(c->dtype, sa, s));
-  WG_TRY(wg_conv(c, {"spec", L[5], 128, WG_MAP_ID, 1, L[5], 128, "first_conv", 768, 3, 1, 0, nullptr, 0, 0, nullptr, 0, 1, 0, "uin"},
+// upsample.0's block1 / block2[0] from "uin" (wavegrad.py:92-97): no FiLM reaches them
+static int wg_up0_head(sddm_ctx* c, int B, const int64_t* L, hipStream_t s) {
+  const wg::Up& u = c->wgs->v->up[0];
+  WG_TRY(wg_conv(c, {"uin", L[5], u.ci, WG_MAP_ID, 1, L[5], u.ci, "upsample.0.block1", u.h, 1, 1, 0, nullptr, 0, 0, nullptr, 0, 1, 0, "u0b1"},
                  B, nullptr, 0, nullptr, s));
-  const wg::Up& u = wg::kUp[0];
-  WG_TRY(wg_conv(c, {"uin", L[5], 768, WG_MAP_ID, 1, L[5], 768, "upsample.0.block1", u.h, 1, 1, 0, nullptr, 0, 0, nullptr, 0, 1, 0, "u0b1"},
-                 B, nullptr, 0, nullptr, s));
-  WG_TRY(wg_conv(c, {"uin", L[5], 768, WG_MAP_UP, u.f, L[4], 768, "upsample.0.block2.0", u.h, 3, u.dil[0], 1, nullptr, 0, 0,
+  WG_TRY(wg_conv(c, {"uin", L[5], u.ci, WG_MAP_UP, u.f, L[4], u.ci, "upsample.0.block2.0", u.h, 3, u.dil[0], 1, nullptr, 0, 0,
                      nullptr, 0, 1, 0, "u0y0"}, B, nullptr, 0, nullptr, s));
   return SDDM_OK;
 }
 
-// one WaveGrad forward: audio [B][N] fp32 -> eps [B][N] fp32 (aoff "eps")
-static int wg_network(sddm_ctx* c, const float* audio, int B, int F, const float* enc, int enc_per_b, int* t_dev,
-                      hipStream_t s) {
+// step-invariant work of one call.  WaveGrad: cond = spectrogram [B][128][F] -> first_conv
+// (wavegrad.py:175).  DenoiseWaveGrad1: cond = waveform [B][N] -> downsample_x (wavegrad.py:234-236;
+// its levels 1-4 borrow the y_t branch's buffers, which the steps overwrite afterwards).  Both then
+// run upsample.0's block1 / block2[0].  DenoiseWaveGrad3 has no step-invariant work
+static int wg_condition(sddm_ctx* c, const float* cond, int B, int F, hipStream_t s) {
   WGState& d = *c->wgs;
+  const wg::Variant& v = *d.v;
+  if (!v.hoist) return SDDM_OK;
+  int64_t L[6];
+  wg_lengths(v, F, L);
+  if (v.kind == wg::kWaveGrad) {
+    WGSpecArgs sa{cond, d.act.base + d.aoff.at("spec"), B, WGState::kSpecC, F};
+    SDDM_HIP_CHECK(launch_wg_spec(c->dtype, sa, s));
+    WG_TRY(wg_conv(c, {"spec", L[5], 128, WG_MAP_ID, 1, L[5], 128, "first_conv", v.up[0].ci, 3, 1, 0, nullptr, 0, 0, nullptr, 0, 1, 0, "uin"},
+                   B, nullptr, 0, nullptr, s));
+  } else {
+    const Arena& W = c->warena;
+    WGFirstArgs fa{cond, W.at<float>(d.woff.at("downsample_x.0.w")), W.at<float>(d.woff.at("downsample_x.0.b")),
+                   d.act.base + d.aoff.at("d0"), B, (int)L[0], nullptr};
+    SDDM_HIP_CHECK(launch_wg_first(c->dtype, fa, s));
+    std::string x = "d0";
+    for (int i = 1; i < 5; ++i) {
+      const std::string si = std::to_string(i), o = "d" + si;
+      WG_TRY(wg_dblock(c, "downsample_x." + si + ".", x.c_str(), L[i - 1], v.down[i], L[i], o, o.c_str(), B, s));
+      x = o;
+    }
+    WG_TRY(wg_dblock(c, v.bottom_key, x.c_str(), L[4], v.bottom, L[5], "bn", "uin", B, s));
+  }
+  return wg_up0_head(c, B, L, s);
+}
+
+// one forward of the y_t branch and the decoder: audio [B][N] fp32 (and, for DenoiseWaveGrad3, the
+// condition waveform [B][N]) -> eps [B][N] fp32 (aoff "eps")
+static int wg_network(sddm_ctx* c, const float* cond, const float* audio, int B, int F, const float* enc, int enc_per_b,
+                      int* t_dev, hipStream_t s) {
+  WGState& d = *c->wgs;
+  const wg::Variant& v = *d.v;
   const Arena& W = c->warena;
   int64_t L[6];
-  wg_lengths(F, L);
-  WGFirstArgs fa{audio, W.at<float>(d.woff.at("downsample.0.w")), W.at<float>(d.woff.at("downsample.0.b")),
-                 d.act.base + d.aoff.at("d0"), B, (int)L[0], t_dev};
-  SDDM_HIP_CHECK(launch_wg_first(c->dtype, fa, s));
+  wg_lengths(v, F, L);
+  if (v.stem_ci == 2) {                                  // cat([y_t, x]) (wavegrad.py:343)
+    WGFirst2Args fa{audio, cond, W.at<float>(d.woff.at("downsample.0.w")), W.at<float>(d.woff.at("downsample.0.b")),
+                    d.act.base + d.aoff.at("d0"), B, (int)L[0], t_dev};
+    SDDM_HIP_CHECK(launch_wg_first2(c->dtype, fa, s));
+  } else {
+    WGFirstArgs fa{audio, W.at<float>(d.woff.at("downsample.0.w")), W.at<float>(d.woff.at("downsample.0.b")),
+                   d.act.base + d.aoff.at("d0"), B, (int)L[0], t_dev};
+    SDDM_HIP_CHECK(launch_wg_first(c->dtype, fa, s));
+  }
   std::string x = "d0";
   for (int i = 0; i < 5; ++i) {
     const std::string si = std::to_string(i);
-    if (i > 0) {                                         // DBlock (wavegrad.py:126-137)
-      const wg::Down& dn = wg::kDown[i];
-      const std::string p = "downsample." + si + ".", o = "d" + si;
-      const char* xs = x.c_str();
-      WG_TRY(wg_conv(c, {xs, L[i - 1], dn.ci, WG_MAP_DOWN, dn.f, L[i], dn.ci, p + "residual_dense", dn.co, 1, 1, 0, nullptr, 0, 0,
-                         nullptr, 0, 1, 0, (o + "r").c_str()}, B, enc, enc_per_b, t_dev, s));
-      WG_TRY(wg_conv(c, {xs, L[i - 1], dn.ci, WG_MAP_DOWN, dn.f, L[i], dn.ci, p + "conv.0", dn.co, 3, 1, 1, nullptr, 0, 0,
-                         nullptr, 0, 1, 0, (o + "a").c_str()}, B, enc, enc_per_b, t_dev, s));
-      WG_TRY(wg_conv(c, {(o + "a").c_str(), L[i], dn.co, WG_MAP_ID, 1, L[i], dn.co, p + "conv.1", dn.co, 3, 2, 1, nullptr, 0, 0,
-                         nullptr, 0, 1, 0, (o + "b").c_str()}, B, enc, enc_per_b, t_dev, s));
-      WG_TRY(wg_conv(c, {(o + "b").c_str(), L[i], dn.co, WG_MAP_ID, 1, L[i], dn.co, p + "conv.2", dn.co, 3, 4, 1, nullptr, 0, 0,
-                         (o + "r").c_str(), WG_MAP_ID, 1, L[i], o.c_str()}, B, enc, enc_per_b, t_dev, s));
+    if (i > 0) {
+      const std::string o = "d" + si;
+      WG_TRY(wg_dblock(c, "downsample." + si + ".", x.c_str(), L[i - 1], v.down[i], L[i], o, o.c_str(), B, s));
       x = o;
     }
-    const wg::Film& fm = wg::kFilm[i];                   // FiLM (wavegrad.py:66-71)
+    const wg::Film& fm = v.film[i];                      // FiLM (wavegrad.py:66-71)
     const std::string p = "film." + si + ".", o = "f" + si;
     WG_TRY(wg_conv(c, {x.c_str(), L[i], fm.ci, WG_MAP_ID, 1, L[i], fm.ci, p + "input_conv", fm.ci, 3, 1, 0, nullptr, 1,
-                       wg::kEncOff[i], nullptr, 0, 1, 0, (o + "a").c_str()}, B, enc, enc_per_b, t_dev, s));
+                       v.enc_off[i], nullptr, 0, 1, 0, (o + "a").c_str()}, B, enc, enc_per_b, t_dev, s));
     WG_TRY(wg_conv(c, {(o + "a").c_str(), L[i], fm.ci, WG_MAP_ID, 1, L[i], fm.ci, p + "output_conv", 2 * fm.co, 3, 1, 0, nullptr,
                        0, 0, nullptr, 0, 1, 0, o.c_str()}, B, enc, enc_per_b, t_dev, s));
   }
+  if (!v.hoist) {                                        // bottleneck (wavegrad.py:349), then upsample.0 in full
+    WG_TRY(wg_dblock(c, v.bottom_key, x.c_str(), L[4], v.bottom, L[5], "bn", "uin", B, s));
+  }
   x = "uin";
   for (int i = 0; i < 5; ++i) {                           // UBlock (wavegrad.py:91-112)
-    const wg::Up& u = wg::kUp[i];
+    const wg::Up& u = v.up[i];
     const std::string si = std::to_string(i), p = "upsample." + si + ".", o = "u" + si;
     const std::string film = "f" + std::to_string(4 - i);
     const int64_t lin = L[5 - i], lout = L[4 - i];
@@ -278,20 +372,21 @@ static int wg_network(sddm_ctx* c, const float* audio, int B, int F, const float
     // block3.1's inputs runs in their producers' epilogues (post_film: y0 holds leaky(film(block2.0
     // out)), m holds leaky(film(x)), z holds leaky(film(block3.0 out))), so shift / scale are read
     // once per element instead of once per 128-channel block of the consumer (upsample.1: 1137 ->
-    // 962 us per step at B=64).  upsample.0's block2.0 is step-invariant (wg_condition), so its
-    // block2.1 keeps the FiLM in the staging (pre 2).  The 128 / 256-channel UBlocks keep the
+    // 962 us per step at B=64).  Where upsample.0's block2.0 is step-invariant (wg_condition: WaveGrad,
+    // DenoiseWaveGrad1), its block2.1 keeps the FiLM in the staging (pre 2).  The 128 / 256-channel UBlocks keep the
     // staged FiLM: there the epilogue loads are exposed (all blocks reach their epilogues
     // together) and cost more than the re-reads save (upsample.4: 1324 -> 1675 us)
     const std::string ym = o + "y0", xm = o + "m", xo = o + "x", zo = o + "z", b1 = o + "b1";
     static const int epi_min_h = std::getenv("SDDM_WG_EPI_MIN_H") ? std::atoi(std::getenv("SDDM_WG_EPI_MIN_H")) : 512;
     const bool epi = u.h >= epi_min_h;
-    if (i > 0) {
+    const bool head_done = i == 0 && v.hoist;            // wg_condition ran block1 / block2[0] (plain, no epilogue FiLM)
+    if (!head_done) {
       WG_TRY(wg_conv(c, {x.c_str(), lin, u.ci, WG_MAP_ID, 1, lin, u.ci, p + "block1", u.h, 1, 1, 0, nullptr, 0, 0, nullptr, 0, 1, 0,
                          b1.c_str()}, B, enc, enc_per_b, t_dev, s));
       WG_TRY(wg_conv(c, {x.c_str(), lin, u.ci, WG_MAP_UP, u.f, lout, u.ci, p + "block2.0", u.h, 3, u.dil[0], 1, nullptr, 0, 0,
                          nullptr, 0, 1, 0, ym.c_str(), epi ? film.c_str() : nullptr, epi ? 1 : 0}, B, enc, enc_per_b, t_dev, s));
     }
-    const bool pre21 = !epi || i == 0;
+    const bool pre21 = !epi || head_done;
     WG_TRY(wg_conv(c, {ym.c_str(), lout, u.h, WG_MAP_ID, 1, lout, u.h, p + "block2.1", u.h, 3, u.dil[1], pre21 ? 2 : 0,
                        pre21 ? film.c_str() : nullptr, 0, 0, b1.c_str(), WG_MAP_UP, u.f, lin, xo.c_str(),
                        epi ? film.c_str() : nullptr, epi ? 2 : 0, epi ? xm.c_str() : nullptr}, B, enc, enc_per_b, t_dev, s));
@@ -302,7 +397,8 @@ static int wg_network(sddm_ctx* c, const float* audio, int B, int F, const float
                        epi ? nullptr : film.c_str(), 0, 0, xo.c_str(), WG_MAP_ID, 1, lout, o.c_str()}, B, enc, enc_per_b, t_dev, s));
     x = o;
   }
-  WG_TRY(wg_conv(c, {x.c_str(), L[0], 128, WG_MAP_ID, 1, L[0], 128, "last_conv", 1, 3, 1, 0, nullptr, 0, 0, nullptr, 0, 1, 0, "eps"},
+  const int cl = v.up[4].h;
+  WG_TRY(wg_conv(c, {x.c_str(), L[0], cl, WG_MAP_ID, 1, L[0], cl, "last_conv", 1, 3, 1, 0, nullptr, 0, 0, nullptr, 0, 1, 0, "eps"},
                  B, enc, enc_per_b, t_dev, s));
   return SDDM_OK;
 }
@@ -312,8 +408,8 @@ static int wg_enc(sddm_ctx* c, const float* noise_levels, int rows, float* out, 
   WGEncArgs e{};
   e.noise_levels = noise_levels; e.table = c->warena.at<float>(d.off_tables) + (size_t)3 * (c->T + 1);
   e.time_step_mode = c->noise_time_step; e.R = rows;
-  e.ev = c->warena.at<float>(d.woff.at("enc.ev")); e.stride = WGState::kEncN; e.n = WGState::kEncN;
-  for (int i = 0; i < 5; ++i) { e.dims[i] = wg::kFilm[i].ci; e.offs[i] = wg::kEncOff[i]; }
+  e.ev = c->warena.at<float>(d.woff.at("enc.ev")); e.stride = d.v->enc_n; e.n = d.v->enc_n;
+  for (int i = 0; i < 5; ++i) { e.dims[i] = d.v->film[i].ci; e.offs[i] = d.v->enc_off[i]; }
   e.out = out;
   SDDM_HIP_CHECK(launch_wg_enc(e, s));
   return SDDM_OK;
@@ -321,27 +417,32 @@ static int wg_enc(sddm_ctx* c, const float* noise_levels, int rows, float* out, 
 
 static int wg_check_shape(sddm_ctx* c, int64_t B, int64_t N, int* F) {
   if (B < 1 || B > 65535) FAIL(SDDM_ERR_INVALID_ARG, "batch %lld", (long long)B);
-  if (c->hop_samples != WGState::kHop)
-    FAIL(SDDM_ERR_SHAPE, "hop_samples %d: WaveGrad upsamples the spectrogram x300 (wavegrad.py:157-163)", c->hop_samples);
-  if (N < WGState::kHop || N % WGState::kHop)
-    FAIL(SDDM_ERR_SHAPE, "%lld samples is not hop_samples (300) x frames", (long long)N);
-  *F = (int)(N / WGState::kHop);
+  const wg::Variant& v = *c->wgs->v;
+  if (c->hop_samples != v.hop)
+    FAIL(SDDM_ERR_SHAPE, "hop_samples %d: %s resamples x%d (wavegrad.py:157-163, 217-223, 332-338)", c->hop_samples, v.name, v.hop);
+  if (N < v.hop || N % v.hop)
+    FAIL(SDDM_ERR_SHAPE, "%lld samples is not a positive multiple of %s's hop (%d)", (long long)N, v.name, v.hop);
+  *F = (int)(N / v.hop);
   return SDDM_OK;
 }
 
-// SDDM_spectrogram.infer (model.py:212-257) with WaveGrad: spec [B][128][F], out [B][1][300 F]
-static int wg_sample(sddm_ctx* c, const float* spec, int64_t B, int64_t N, uint64_t seed, int64_t row_offset, float* out,
+// The reverse loop over a network of the family.  WaveGrad: SDDM_spectrogram.infer (model.py:212-257),
+// cond = spectrogram [B][128][F], x_T = randn, p_transition 'original' (the context's init / transition
+// modes are those).  DenoiseWaveGrad1 / 3: SDDM.infer (model.py:50-124), cond = waveform [B][1][N], the
+// initial state and the transition of the context's p_transition.  out [B][1][hop F]
+static int wg_sample(sddm_ctx* c, const float* cond, int64_t B, int64_t N, uint64_t seed, int64_t row_offset, float* out,
                      float* record, int sample_inter, const float* noise, hipStream_t s) {
   WGState& d = *c->wgs;
   int F = 0;
   WG_TRY(wg_check_shape(c, B, N, &F));
   WG_TRY(wg_prepare(c, (int)B, F));
   const int T = c->T;
+  const float* wave = d.v->kind == wg::kWaveGrad ? nullptr : cond;   // the condition as a waveform, or none
   float* enctab = c->warena.at<float>(d.off_enctab);
   WG_TRY(wg_enc(c, nullptr, T + 1, enctab, s));
-  WG_TRY(wg_condition(c, spec, (int)B, F, s));
-  InitArgs ia{};                                       // x_T = randn(B, 1, hop F) (model.py:216)
-  ia.mode = 0; ia.cond = nullptr; ia.out = out; ia.total = B * N; ia.N = N; ia.T = T;
+  WG_TRY(wg_condition(c, cond, (int)B, F, s));
+  InitArgs ia{};                                       // x_T (model.py:57-68, 216)
+  ia.mode = c->init_mode; ia.cond = wave; ia.out = out; ia.total = B * N; ia.N = N; ia.T = T;
   ia.co = c->coef(); ia.seed = seed; ia.row_offset = row_offset; ia.noise = noise;
   SDDM_HIP_CHECK(launch_init_state(ia, s));
   StepParams* sp = c->warena.at<StepParams>(d.off_sp);
@@ -349,9 +450,9 @@ static int wg_sample(sddm_ctx* c, const float* spec, int64_t B, int64_t N, uint6
   int64_t nrec = 0;
   float* eps = d.act.at<float>(d.aoff.at("eps"));
   for (int t = T; t >= 1; --t) {
-    WG_TRY(wg_network(c, out, (int)B, F, enctab, 0, &sp->t, s));
-    TransArgs ta{};                                    // p_transition (diffusion.py:177-190)
-    ta.mode = SDDM_TR_ORIGINAL; ta.x_t = out; ta.eps = eps; ta.cond = nullptr; ta.out = out;
+    WG_TRY(wg_network(c, wave, out, (int)B, F, enctab, 0, &sp->t, s));
+    TransArgs ta{};                                    // p_transition* (diffusion.py:164-223)
+    ta.mode = c->tr_mode; ta.x_t = out; ta.eps = eps; ta.cond = wave; ta.out = out;
     ta.total = B * N; ta.N = N; ta.t = t; ta.t_dev = &sp->t; ta.co = c->coef(); ta.seed = seed; ta.row_offset = row_offset;
     ta.noise = noise; ta.noise_ld = B * N;
     SDDM_HIP_CHECK(launch_transition(ta, s));
@@ -363,8 +464,9 @@ static int wg_sample(sddm_ctx* c, const float* spec, int64_t B, int64_t N, uint6
   return SDDM_OK;
 }
 
-// one WaveGrad forward (wavegrad.py:167-179): spec [B][128][F], audio [B][N], noise level [B] -> eps [B][N]
-static int wg_forward(sddm_ctx* c, const float* spec, const float* x_t, const float* noise_level, int64_t B, int64_t N,
+// one forward (wavegrad.py:167-179, 226-242, 341-353): cond = spectrogram [B][128][F] (WaveGrad) or
+// waveform [B][N] (DenoiseWaveGrad1 / 3), audio [B][N], noise level [B] -> eps [B][N]
+static int wg_forward(sddm_ctx* c, const float* cond, const float* x_t, const float* noise_level, int64_t B, int64_t N,
                       float* eps_out, hipStream_t s) {
   WGState& d = *c->wgs;
   int F = 0;
@@ -372,8 +474,8 @@ static int wg_forward(sddm_ctx* c, const float* spec, const float* x_t, const fl
   WG_TRY(wg_prepare(c, (int)B, F));
   float* encb = d.act.at<float>(d.aoff.at("encb"));
   WG_TRY(wg_enc(c, noise_level, (int)B, encb, s));
-  WG_TRY(wg_condition(c, spec, (int)B, F, s));
-  WG_TRY(wg_network(c, x_t, (int)B, F, encb, 1, nullptr, s));
+  WG_TRY(wg_condition(c, cond, (int)B, F, s));
+  WG_TRY(wg_network(c, d.v->kind == wg::kWaveGrad ? nullptr : cond, x_t, (int)B, F, encb, 1, nullptr, s));
   SDDM_HIP_CHECK(hipMemcpyAsync(eps_out, d.act.at<float>(d.aoff.at("eps")), sizeof(float) * B * N, hipMemcpyDeviceToDevice, s));
   return SDDM_OK;
 }

@@ -93,8 +93,24 @@ def run(config, model, loader, dataset, device, logger=None, seed=None):
     return log
 
 
+def check_num_samples(config):
+    """The waveform-conditioned 1-D networks (DenoiseWaveGrad1 / 3 under arch SDDM) resample by fixed
+    factors, so every chunk must be a positive multiple of the network's hop: fail here, before any
+    data are read, rather than in the first batch."""
+    cfg = config.config if hasattr(config, "config") else config
+    net = getattr(module_network, cfg["network"]["type"], None)
+    hop = getattr(net, "hop_samples", None)
+    if not hop or cfg["arch"]["type"] != "SDDM":
+        return
+    n = cfg.get("num_samples")
+    if not isinstance(n, int) or n < hop or n % hop:
+        raise ValueError(f"num_samples {n}: {cfg['network']['type']} needs a positive multiple of its hop "
+                         f"({hop} samples), e.g. {max(1, round((n if isinstance(n, int) else hop) / hop)) * hop}")
+
+
 def main(config, seed=None, lane_rows=None):
     logger = config.get_logger("infer")
+    check_num_samples(config)
     if "infer_data_loader" not in config.config:                                  # SURVEY Q1
         config.config["infer_data_loader"] = {"type": "InferDataLoader", "args": {"batch_size": 4, "num_workers": 2}}
     infer_dataset = config.init_obj("infer_dataset", module_data, sample_rate=config["sample_rate"],

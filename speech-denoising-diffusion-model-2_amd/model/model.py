@@ -294,6 +294,8 @@ def build_from_config(config, module_diffusion, module_network, module_arch, dev
         network = config.init_obj("network", module_network, **net_kw)
         model = config.init_obj("arch", module_arch, diffusion, network, **arch_kw)
     else:
-        network = config.init_obj("network", module_network, num_samples=cfg["num_samples"])
+        # the reference's default config.json (DenoiseWaveGrad1) has no num_samples: the 1-D
+        # networks take any multiple of their hop and ignore the keyword
+        network = config.init_obj("network", module_network, num_samples=cfg.get("num_samples", -1))
         model = config.init_obj("arch", module_arch, diffusion, network)
     return diffusion, network, model

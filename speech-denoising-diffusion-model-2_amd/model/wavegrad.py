@@ -10,6 +10,16 @@ its Conv1d rejects (4-D input), and WaveGrad's squeezed [B,N] output would broad
 The library applies the adapter (audio = x_t[:, 0], noise level [B], eps -> [B,1,N]); this
 ``forward`` accepts audio as [B,N] (reference) or [B,1,N] and returns ``squeeze``d output like
 the reference (wavegrad.py:179).
+
+DenoiseWaveGrad1 / DenoiseWaveGrad3 (wavegrad.py:184-242, 307-353) are the waveform-conditioned
+variants the reference's default config.json names: ``forward(x, y_t, noise_level)`` with the noisy
+waveform x and the state y_t both [B,1,N] under the plain ``SDDM`` sampler.  N must be a positive
+multiple of ``hop_samples`` (400 = 2*2*4*5*5 and 300 = 2*2*3*5*5: the resample factors of the
+ladder; any other length fails in the reference with a tensor-size mismatch).
+
+Deviation: a single clip (B = 1) works here.  The reference's PositionalEncoding squeezes the
+[1,1,1] noise level to a 0-d tensor that its ``unsqueeze(1)`` rejects (wavegrad.py:37-47), so the
+reference itself runs these networks only with B >= 2.
 """
 from math import log as ln  # noqa: F401  (reference import surface)
 
@@ -139,3 +149,111 @@ class WaveGrad(nn.Module):
         out = torch.empty_like(x)
         self._context(x.device).network_forward(spec, x, nl, out)
         return torch.squeeze(out)
+
+
+class _WaveformDenoiser(nn.Module):
+    """Shared facade of the waveform-conditioned variants: the subclasses build the parameter tree
+    (reference attribute names) and name their hop.  The reference constructors take no arguments;
+    the keyword arguments ConfigParser.init_obj adds (num_samples) are accepted and ignored."""
+
+    hop_samples = None
+
+    def _init_facade(self):
+        self.config_args = {}
+        self.num_samples = -1
+        self.compute_dtype = "float32"
+        self._ctx = None
+        self._ctx_key = None
+
+    def library_config(self):
+        return {"arch": {"type": "SDDM", "args": {}},
+                "diffusion": {"type": "GaussianDiffusion", "args": {"schedule": "linear", "n_timestep": 1}},
+                "network": {"type": type(self).__name__, "args": {}}, "num_samples": -1}
+
+    _context = WaveGrad._context
+
+    @torch.no_grad()
+    def forward(self, x, y_t, noise_level):
+        """x (noisy waveform) and y_t [B, 1, N], N a positive multiple of hop_samples; noise_level
+        with B elements (any shape) -> eps [B, 1, N] (wavegrad.py:226-242, 341-353)."""
+        if not y_t.is_cuda:
+            raise RuntimeError(f"{type(self).__name__} runs on the HIP device; move the tensors to cuda")
+        B = y_t.shape[0]
+        cond = x.reshape(B, 1, -1).contiguous().float()
+        yt = y_t.reshape(B, 1, -1).contiguous().float()
+        if cond.shape != yt.shape:
+            raise RuntimeError(f"condition {tuple(x.shape)} and y_t {tuple(y_t.shape)} differ in size")
+        nl = noise_level.reshape(-1).contiguous().float()
+        if nl.numel() != B:
+            raise RuntimeError(f"noise_level has {nl.numel()} elements for batch {B}")
+        out = torch.empty_like(yt)
+        self._context(yt.device).network_forward(cond, yt, nl, out)
+        return out
+
+
+class DenoiseWaveGrad1(_WaveformDenoiser):
+    """wavegrad.py:184-242: the condition x goes down its own DBlock ladder (downsample_x) to the
+    512-channel input of the first UBlock; y_t's ladder feeds the FiLMs."""
+
+    hop_samples = 400
+
+    def __init__(self, **unused):
+        super().__init__()
+        self.downsample = nn.ModuleList([
+            Conv1d(1, 32, 5, padding=2),
+            DBlock(32, 128, 2),
+            DBlock(128, 128, 2),
+            DBlock(128, 256, 4),
+            DBlock(256, 512, 5)])
+        self.downsample_x = nn.ModuleList([
+            Conv1d(1, 32, 5, padding=2),
+            DBlock(32, 128, 2),
+            DBlock(128, 128, 2),
+            DBlock(128, 256, 4),
+            DBlock(256, 512, 5),
+            DBlock(512, 512, 5)])
+        self.film = nn.ModuleList([
+            FiLM(32, 128),
+            FiLM(128, 128),
+            FiLM(128, 256),
+            FiLM(256, 512),
+            FiLM(512, 512)])
+        self.upsample = nn.ModuleList([
+            UBlock(512, 512, 5, [1, 2, 1, 2]),
+            UBlock(512, 512, 5, [1, 2, 1, 2]),
+            UBlock(512, 256, 4, [1, 2, 4, 8]),
+            UBlock(256, 128, 2, [1, 2, 4, 8]),
+            UBlock(128, 128, 2, [1, 2, 4, 8])])
+        self.last_conv = Conv1d(128, 1, 3, padding=1)
+        self._init_facade()
+
+
+class DenoiseWaveGrad3(_WaveformDenoiser):
+    """wavegrad.py:307-353: cat([y_t, x]) enters one ladder; an extra bottleneck DBlock feeds the
+    first UBlock."""
+
+    hop_samples = 300
+
+    def __init__(self, **unused):
+        super().__init__()
+        self.downsample = nn.ModuleList([
+            Conv1d(2, 32, 5, padding=2),
+            DBlock(32, 128, 2),
+            DBlock(128, 128, 2),
+            DBlock(128, 256, 3),
+            DBlock(256, 512, 5)])
+        self.bottleneck = DBlock(512, 512, 5)
+        self.film = nn.ModuleList([
+            FiLM(32, 128),
+            FiLM(128, 128),
+            FiLM(128, 256),
+            FiLM(256, 512),
+            FiLM(512, 512)])
+        self.upsample = nn.ModuleList([
+            UBlock(512, 512, 5, [1, 2, 1, 2]),
+            UBlock(512, 512, 5, [1, 2, 1, 2]),
+            UBlock(512, 256, 3, [1, 2, 4, 8]),
+            UBlock(256, 128, 2, [1, 2, 4, 8]),
+            UBlock(128, 128, 2, [1, 2, 4, 8])])
+        self.last_conv = Conv1d(128, 1, 3, padding=1)
+        self._init_facade()
