@@ -249,6 +249,7 @@ struct Lane {                         // one row block of the batch: plan + acti
 
 struct DWState;                       // DiffWave path (dw_runtime.h)
 struct WGState;                       // WaveGrad path (wg_runtime.h)
+struct WUState;                       // Waveunet3 path (wu_runtime.h)
 
 struct sddm_ctx {
   int device = 0, dtype = DT_BF16;
@@ -292,6 +293,7 @@ struct sddm_ctx {
   // SDDM_spectrogram + DiffWave
   std::shared_ptr<DWState> dws;
   std::shared_ptr<WGState> wgs;
+  std::shared_ptr<WUState> wus;
   // measured per-layer kernel tables (sddm_set_conv_tuning), each valid for one lane batch /
   // dtype / num_samples: conv_deep tiles per layer name (pixels per block, waves) and the kernel
   // choice (1 strip, 2 tile (a = configuration), 3 deep (a = pixels, b = waves, c = channels))
@@ -490,6 +492,7 @@ static int upload_tables(sddm_ctx* c) {
 
 #include "dw_runtime.h"
 #include "wg_runtime.h"
+#include "wu_runtime.h"
 
 // ---------------------------------------------------------------------------------------------
 // plan: the launch sequence of one UNetModified2 step for batch B
@@ -1094,7 +1097,7 @@ static int ensure_ready(sddm_ctx* c) {
   for (const auto& kv : c->params)
     if (!kv.second.loaded) FAIL(SDDM_ERR_STATE, "parameter %s not loaded", kv.first.c_str());
   if (c->params_dirty) {
-    const int r = c->dws ? dw_upload_weights(c) : (c->wgs ? wg_upload_weights(c) : upload_weights(c));
+    const int r = c->dws ? dw_upload_weights(c) : (c->wgs ? wg_upload_weights(c) : (c->wus ? wu_upload_weights(c) : upload_weights(c)));
     if (r) return r;
   }
   if (c->tables_dirty) {
@@ -1179,6 +1182,7 @@ void sddm_destroy(sddm_ctx* c) {
   c->lanes.clear();
   if (c->dws) c->dws->act.reset();
   if (c->wgs) c->wgs->act.reset();
+  if (c->wus) c->wus->act.reset();
   if (c->ev_in) (void)hipEventDestroy(c->ev_in);
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   c->warena.reset();
@@ -1286,6 +1290,7 @@ int sddm_configure(sddm_ctx* c, const char* json) {
     c->params["diffusion_embedding.embedding_vector"].loaded = true;   // optional (default computed)
     c->dws = d;
     c->wgs.reset();
+    c->wus.reset();
     c->params_dirty = true;
     c->plan_B = -1;
     c->lanes.clear();
@@ -1317,6 +1322,33 @@ int sddm_configure(sddm_ctx* c, const char* json) {
     }
     c->dws.reset();
     c->wgs = ws;
+    c->wus.reset();
+    c->params_dirty = true;
+    c->plan_B = -1;
+    c->lanes.clear();
+    c->warena.reset();
+    c->configured = true;
+    return SDDM_OK;
+  }
+  if (c->net_type == "Waveunet3") {                              // waveunet3.py:314-416, config_waveunet3.json
+    if (c->arch_type != "SDDM") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "Waveunet3 needs arch SDDM (its condition is a waveform)");
+    const int r = wu_check_config(net.at("args"));
+    if (r) return r;
+    c->T = T;
+    c->tables.swap(tabs);
+    c->tables_dirty = true;
+    c->num_samples = -1;
+    c->params.clear();
+    auto us = std::make_shared<WUState>();
+    us->shapes = wu_param_shapes(us->net);
+    for (const auto& kv : us->shapes) {
+      Param p;
+      p.shape = kv.second;
+      c->params[kv.first] = p;
+    }
+    c->dws.reset();
+    c->wgs.reset();
+    c->wus = us;
     c->params_dirty = true;
     c->plan_B = -1;
     c->lanes.clear();
@@ -1328,6 +1360,7 @@ int sddm_configure(sddm_ctx* c, const char* json) {
   if (c->arch_type != "SDDM") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "UNetModified2 under arch '%s'", c->arch_type.c_str());
   c->dws.reset();
   c->wgs.reset();
+  c->wus.reset();
   const Json& na = net.at("args");
   UNetCfg u;
   u.in_channel = (int)na.number("in_channel", 2);
@@ -1460,6 +1493,7 @@ static int sample_impl(sddm_ctx* c, const float* cond, int64_t B, int64_t N, uin
   if (!cond || !out) FAIL(SDDM_ERR_INVALID_ARG, "NULL tensor");
   if (c->dws) return dw_sample(c, cond, B, N, seed, row_offset, out, record, sample_inter, noise, (hipStream_t)stream);
   if (c->wgs) return wg_sample(c, cond, B, N, seed, row_offset, out, record, sample_inter, noise, (hipStream_t)stream);
+  if (c->wus) return wu_sample(c, cond, B, N, seed, row_offset, out, record, sample_inter, noise, (hipStream_t)stream);
   r = prepare_plan(c, B, N);
   if (r) return r;
   hipStream_t user = (hipStream_t)stream;
@@ -1571,6 +1605,7 @@ int sddm_network_forward(sddm_ctx* c, const float* cond, const float* x_t, const
   if (!cond || !x_t || !noise_level || !eps_out) FAIL(SDDM_ERR_INVALID_ARG, "NULL tensor");
   if (c->dws) return dw_forward(c, cond, x_t, noise_level, B, N, eps_out, (hipStream_t)stream);
   if (c->wgs) return wg_forward(c, cond, x_t, noise_level, B, N, eps_out, (hipStream_t)stream);
+  if (c->wus) return wu_forward(c, cond, x_t, noise_level, B, N, eps_out, (hipStream_t)stream);
   r = prepare_plan(c, B, N);
   if (r) return r;
   hipStream_t s = (hipStream_t)stream;

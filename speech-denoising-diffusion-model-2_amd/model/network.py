@@ -1,7 +1,9 @@
 """Network registry resolved by ConfigParser.init_obj('network', module_network, ...)
 (reference model/network.py).  The denoisers on the north-star path: UNetModified2, DiffWave,
 WaveGrad and the waveform-conditioned DenoiseWaveGrad1 / DenoiseWaveGrad3 (the reference's
-DenoiseWaveGrad2 has 4 / 8 / 16-channel levels the MFMA convolution cannot take: not built)."""
+DenoiseWaveGrad2 has 4 / 8 / 16-channel levels the MFMA convolution cannot take: not built), and
+the 1-D Wave-U-Net Waveunet3 at the arguments of config_waveunet3.json."""
 from .UNetModified2 import UNetModified2  # noqa: F401
 from .diffwave import DiffWave  # noqa: F401
 from .wavegrad import DenoiseWaveGrad1, DenoiseWaveGrad3, WaveGrad  # noqa: F401
+from .waveunet3 import Waveunet3  # noqa: F401
