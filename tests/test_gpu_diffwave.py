@@ -71,6 +71,12 @@ def test_diffwave_row_sharding_is_bit_identical(torch_cuda):
     assert torch.equal(full, torch.cat([a, b]))
 
 
+def _tile_worst(eps_row, ref_row):
+    """Worst 128-sample tile of a row: rms(tile error) / rms(ref row) (a localised error shows here)."""
+    e = (eps_row.astype(np.float64) - ref_row).reshape(-1, 128)
+    return float(np.sqrt(np.mean(e ** 2, axis=1)).max() / rms(ref_row, 0))
+
+
 def _dw_rows(B, F, seed):
     rng = np.random.default_rng(seed)
     spec = rng.uniform(0, 1, (B, 513, F)).astype(np.float32)          # SURVEY §8d: U[0,1]
@@ -92,7 +98,8 @@ def test_diffwave_config3_geometry(torch_cuda, dtype, tol):
                       torch.from_numpy(steps).reshape(-1, 1, 1).cuda()).cpu().numpy()
     for b in range(B):
         err = rms(eps[b], ref[b])
-        print(f"{dtype} row {b} step {steps[b]:.0f}: rms {err:.3e} (ref rms {rms(ref[b], 0):.3f})")
+        print(f"{dtype} row {b} step {steps[b]:.0f}: rms {err:.3e} (ref rms {rms(ref[b], 0):.3f}), "
+              f"worst tile {_tile_worst(eps[b], ref[b]):.3e} of the row rms")
         assert err <= tol * max(1.0, rms(ref[b], 0))
 
 
@@ -128,7 +135,8 @@ def test_diffwave_short_clips_dilation_chains(torch_cuda, dtype, tol, F):
                       torch.from_numpy(steps).reshape(-1, 1, 1).cuda()).cpu().numpy()
     for b in range(B):
         err = rms(eps[b], ref[b])
-        print(f"{dtype} F={F} row {b}: rms {err:.3e} (ref rms {rms(ref[b], 0):.3f})")
+        print(f"{dtype} F={F} row {b}: rms {err:.3e} (ref rms {rms(ref[b], 0):.3f}), "
+              f"worst tile {_tile_worst(eps[b], ref[b]):.3e} of the row rms")
         assert np.isfinite(eps[b]).all() and err <= tol * max(1.0, rms(ref[b], 0))
 
 

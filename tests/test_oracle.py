@@ -144,6 +144,35 @@ def test_diffwave_oracle_sampling_matches_reference():
     assert np.sqrt(np.mean((out - z[f"{k}/out"]) ** 2)) <= 1e-5
 
 
+def test_diffwave_emulation_without_rounding_is_the_oracle():
+    """tests/_dw_emul.py (the yardstick of the 16-bit per-tile bounds in test_gpu_diffwave_paths.py)
+    restates oracle.diffwave.forward from its pieces: with no storage type it is the oracle bit for
+    bit, also on a second call that takes the conditioner from its per-spectrogram cache; with one,
+    it differs, by less than the 16-bit bars of test_gpu_diffwave.py (which must sit above rounding)."""
+    from oracle import diffwave as dw
+    from _dw_emul import Emul
+    from _helpers import diffwave_params
+    rng = np.random.default_rng(17)
+    B, F = 2, 2
+    spec = rng.uniform(0, 1, (B, 513, F)).astype(np.float32)
+    audio = rng.standard_normal((B, 1, 256 * F)).astype(np.float32)
+    steps = rng.integers(1, 201, B).astype(np.float32)
+    P = diffwave_params()
+    ref = dw.forward(P, spec, audio, steps)
+    e = Emul(P, None)
+    assert np.array_equal(e(spec, audio, steps), ref)
+    assert np.array_equal(e(spec, audio, steps), ref)            # cached conditioner
+    audio2 = rng.standard_normal((B, 1, 256 * F)).astype(np.float32)
+    assert np.array_equal(e(spec, audio2, steps + 1), dw.forward(P, spec, audio2, steps + 1))
+    spec2 = rng.uniform(0, 1, (B, 513, F)).astype(np.float32)    # another spectrogram: cache refilled
+    assert np.array_equal(e(spec2, audio, steps), dw.forward(P, spec2, audio, steps))
+    scale = max(1.0, rms(ref, 0))
+    for dtype, bar in (("bfloat16", 3e-2), ("float16", 5e-3)):
+        err = rms(Emul(P, dtype)(spec, audio, steps), ref)
+        print(f"{dtype}: storage rounding alone {err / scale:.3e} of the row rms")
+        assert 0 < err < bar * scale
+
+
 # ---------------- WaveGrad (reference model/wavegrad.py) ----------------
 def test_wavegrad_oracle_matches_reference_goldens():
     from oracle import wavegrad as wg
