@@ -80,6 +80,94 @@ template <> __device__ __forceinline__ void store4p<bf16_t>(bf16_t* p, f32x2 a, 
   const bf16x2_t x = __builtin_convertvector(a, bf16x2_t), y = __builtin_convertvector(b, bf16x2_t);
   *(u32x2_t*)p = u32x2_t{__builtin_bit_cast(unsigned int, x), __builtin_bit_cast(unsigned int, y)};
 }
+// ---------------------------------------------------------------------------------------------
+// Output-activation store flavours (DESIGN.md §3 "Store flavours", profiles/store_flavour_*.txt).
+// A plain store leaves its line dirty in the writing XCD's L2 and the dirty lines are written back
+// at the kernel boundary, in front of the dependent launch (tools/mb_boundary.hip: 1.3 us behind
+// 2 MB, 5.4 us behind 34 MB); a write-through store (the sc1 cache bit) sends the bytes on while
+// the kernel still computes.  Two compile-time switches per kernel family (A/B builds with
+// SDDM_EXTRA_DEFS; no runtime branch around the stores, no kernel argument):
+//   SDDM_WT_<family>    1: write-through stores (16-bit storage types; fp32 activations, GroupNorm
+//                       statistics, x_t and the final kernel's output stay plain)
+//   SDDM_ST16_<family>  1: 16 bytes (8 channels) per lane instead of 8 (below)
+// 8-byte write-through stores cost 2.5x the plain ones in the producer and lost in every family;
+// 16-byte write-through stores won in conv_in and the strip kernels and lost in the tile kernels
+// (plain 16-byte stores were neutral everywhere); the deep kernels, whose outputs are small, were
+// neutral at 8 bytes and keep their epilogue.  The defaults are the winners.
+//   family  STRIP conv_strip_impl.h   TILE conv_tile.hip   DEEP conv_deep.hip   IN conv_in (kernels.hip)
+// ---------------------------------------------------------------------------------------------
+#ifndef SDDM_WT_STRIP
+#define SDDM_WT_STRIP 1
+#endif
+#ifndef SDDM_WT_TILE
+#define SDDM_WT_TILE 0
+#endif
+#ifndef SDDM_WT_DEEP
+#define SDDM_WT_DEEP 0
+#endif
+#ifndef SDDM_WT_IN
+#define SDDM_WT_IN 1
+#endif
+// 8 bytes write-through: a relaxed agent-scope atomic store (global_store_dwordx2 sc1), counted in
+// vmcnt by the compiler like any other store
+typedef __attribute__((address_space(1))) unsigned long long gu64_t;
+__device__ __forceinline__ void store8b_wt(void* p, unsigned long long v) {
+  __hip_atomic_store((gu64_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <bool WT, typename T> __device__ __forceinline__ void store4(T* p, float a, float b, float c, float d) {
+  if constexpr (WT && sizeof(T) == 2) {
+    typedef T vec4 __attribute__((ext_vector_type(4)));
+    store8b_wt(p, __builtin_bit_cast(unsigned long long, vec4{(T)a, (T)b, (T)c, (T)d}));
+  } else {
+    store4<T>(p, a, b, c, d);
+  }
+}
+template <bool WT, typename T> __device__ __forceinline__ void store4p(T* p, f32x2 a, f32x2 b) {
+  if constexpr (WT && sizeof(T) == 2) {
+    typedef T vec2 __attribute__((ext_vector_type(2)));
+    typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+    const vec2 x = __builtin_convertvector(a, vec2), y = __builtin_convertvector(b, vec2);
+    store8b_wt(p, __builtin_bit_cast(unsigned long long,
+                                     u32x2_t{__builtin_bit_cast(unsigned int, x), __builtin_bit_cast(unsigned int, y)}));
+  } else {
+    store4p<T>(p, a, b);
+  }
+}
+// 16-byte epilogue stores (16-bit T): SDDM_ST16_<family> = 1 maps MFMA row r of fragment fc of a
+// fragment pair to output channel 8 (r / 4) + 4 fc + r % 4 (pair_channel), so a lane's two
+// accumulators are 8 consecutive channels and leave in one store.  The map only renames which row
+// computes which channel: every element keeps its K order and every statistic its pixel order.
+#ifndef SDDM_ST16_IN
+#define SDDM_ST16_IN 1
+#endif
+#ifndef SDDM_ST16_STRIP
+#define SDDM_ST16_STRIP 1
+#endif
+#ifndef SDDM_ST16_TILE
+#define SDDM_ST16_TILE 0
+#endif
+__host__ __device__ constexpr int pair_channel(int fc, int r) { return 8 * (r / 4) + 4 * (fc & 1) + r % 4 + 32 * (fc / 2); }
+// position c of a block's weight slab (= MFMA row c % 16 of the block's fragment c / 16) -> the
+// block's channel computed there.  The strip and tile kernels apply it where they fill the slab
+// (each lane's global source address), so the weight images keep their channel order.
+template <bool ST16> __device__ constexpr int slab_channel(int c) { return ST16 ? pair_channel(c >> 4, c & 15) : c; }
+typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+// buffer resource of one output image for the write-through 16-byte form (stores past `bytes` are dropped)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t out_rsrc(void* base, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000);
+}
+template <typename T> __device__ __forceinline__ unsigned int pack2(f32x2 a) {
+  typedef T vec2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned int, __builtin_convertvector(a, vec2));
+}
+// 8 consecutive channels (four packed pairs) at byte offset `off` of the image `base` / `rs`
+template <bool WT, typename T>
+__device__ __forceinline__ void store8p(char* base, __amdgpu_buffer_rsrc_t rs, unsigned off, f32x2 a, f32x2 b, f32x2 c, f32x2 d) {
+  static_assert(sizeof(T) == 2, "16-byte stores of 8 channels: 16-bit storage types");
+  const u32x4_t v = u32x4_t{pack2<T>(a), pack2<T>(b), pack2<T>(c), pack2<T>(d)};
+  if constexpr (WT) __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)off, 0, 16);   // aux 16 = sc1
+  else *(u32x4_t*)(base + off) = v;
+}
 // bf16 / f16 / f32 pair -> two floats
 template <typename T> __device__ __forceinline__ f32x2 unpack2(T a, T b) { return f32x2{to_f32<T>(a), to_f32<T>(b)}; }
 template <typename T> __device__ __forceinline__ f32x4 load4(const T* p);

@@ -413,7 +413,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv_deep_kernel(ConvArgs a) 
       float d[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) d[i] = s[i] + idr[it][i];
-      store4<T>(out + ((y0 + py) * gWo + (x0 + px)) * gCout, d[0] + bb[0], d[1] + bb[1], d[2] + bb[2], d[3] + bb[3]);
+      store4<SDDM_WT_DEEP != 0, T>(out + ((y0 + py) * gWo + (x0 + px)) * gCout, d[0] + bb[0], d[1] + bb[1], d[2] + bb[2], d[3] + bb[3]);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {                    // sums about the shift bb (the same for
         s1[i] += d[i];                                 // every thread of a channel: they add)

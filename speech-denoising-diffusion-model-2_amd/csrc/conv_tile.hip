@@ -46,6 +46,9 @@ __global__ __launch_bounds__(64 * WPX * WCO) void conv_tile_kernel(ConvArgs a) {
   constexpr int MT = WPX * FP * 16, NB = WCO * FC * 16;
   constexpr int WCH = 576 * NB;                            // LDS bytes of one 3x3 weight chunk
   static_assert(sizeof(T) == 2, "conv_tile is the 16-bit path");
+  // 16-byte epilogue stores (conv_common.h): each wave's fragments pair up (FC even), so a wave's
+  // first slab position cw0 is a multiple of 32 and the block-level map is the wave-level one
+  constexpr bool ST16 = SDDM_ST16_TILE != 0 && FC % 2 == 0;
   typedef T vec4 __attribute__((ext_vector_type(4)));
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // layer geometry: compile-time for a specialised shape (SH > 0, kTileShapes), else the arguments
@@ -92,7 +95,7 @@ __global__ __launch_bounds__(64 * WPX * WCO) void conv_tile_kernel(ConvArgs a) {
   for (int fc = 0; fc < FC; ++fc)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {                          // unconditional loads (no wait at a join)
-      const int co = n0 + cw0 + fc * 16 + 4 * g + i;
+      const int co = n0 + cw0 + slab_channel<ST16>(fc * 16 + 4 * g + i);
       const float bv = a.bias[co], tv = trow[co];
       bb[fc][i] = bv + (a.temb ? tv : 0.f);
     }
@@ -120,7 +123,7 @@ __global__ __launch_bounds__(64 * WPX * WCO) void conv_tile_kernel(ConvArgs a) {
     for (int fp = 0; fp < FP; ++fp) {
       const int po = ident ? ((y0 + ppy[fp]) * gWo + (x0 + ppx[fp])) * gCout : 0;
 #pragma unroll
-      for (int fc = 0; fc < FC; ++fc) r1[fp][fc] = *(const vec4*)(rs + po + (ident ? n0 + cw0 + fc * 16 + 4 * g : 0));
+      for (int fc = 0; fc < FC; ++fc) r1[fp][fc] = *(const vec4*)(rs + po + (ident ? n0 + cw0 + slab_channel<ST16>(fc * 16 + 4 * g) : 0));
     }
   }
   // staging geometry of this thread's 3x3 units (the same for every chunk): unit u = tid + j NT
@@ -178,7 +181,7 @@ __global__ __launch_bounds__(64 * WPX * WCO) void conv_tile_kernel(ConvArgs a) {
                          : (const char*)a.wgt_t + (size_t)k * 36 * gCout * 16;
     for (int u0 = wv * 64; u0 < nw; u0 += NT) {
       const int u = u0 + lane, r = u / NB, co = u - r * NB;
-      glds16(ws + ((size_t)r * gCout + n0 + co) * 16, dst + u0 * 16);
+      glds16(ws + ((size_t)r * gCout + n0 + slab_channel<ST16>(co)) * 16, dst + u0 * 16);
     }
   };
   // weight chunk k through registers (WR): WU 16-byte units per thread, loaded with the raw halo
@@ -196,7 +199,7 @@ __global__ __launch_bounds__(64 * WPX * WCO) void conv_tile_kernel(ConvArgs a) {
 #pragma unroll
     for (int i = 0; i < WU; ++i) {
       const int u = tid + i * NT, uu = u < nw ? u : 0, r = uu / NB, co = uu - r * NB;
-      wr[i] = *(const f32x4*)(ws + ((size_t)r * gCout + n0 + co) * 16);
+      wr[i] = *(const f32x4*)(ws + ((size_t)r * gCout + n0 + slab_channel<ST16>(co)) * 16);
     }
   };
   auto store_w = [&](int k, int buf) {
@@ -334,6 +337,7 @@ __global__ __launch_bounds__(64 * WPX * WCO) void conv_tile_kernel(ConvArgs a) {
 
   // ---------------- epilogue ----------------
   T* out = (T*)a.out + (size_t)b * img_out * gCout;
+  [[maybe_unused]] const __amdgpu_buffer_rsrc_t ors = out_rsrc(out, (unsigned)(img_out * gCout) * (unsigned)sizeof(T));
   float s1[FC][4], s2[FC][4], nl = 0.f;
 #pragma unroll
   for (int fc = 0; fc < FC; ++fc)
@@ -344,13 +348,26 @@ __global__ __launch_bounds__(64 * WPX * WCO) void conv_tile_kernel(ConvArgs a) {
     if (!pok[fp]) continue;
     nl += 1.f;
     const int po = ((y0 + ppy[fp]) * gWo + (x0 + ppx[fp])) * gCout;
+    [[maybe_unused]] f32x2 pv0, pv1;                       // the even fragment of a pair (ST16)
 #pragma unroll
     for (int fc = 0; fc < FC; ++fc) {
       const int co = n0 + cw0 + fc * 16 + 4 * g;
       float d[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) d[i] = acc[fp][fc][i] + (ident ? to_f32<T>(r1[fp][fc][i]) : 0.f);
-      if (!(dbg & 128)) store4<T>(out + po + co, d[0] + bb[fc][0], d[1] + bb[fc][1], d[2] + bb[fc][2], d[3] + bb[fc][3]);
+      if constexpr (ST16) {                                // a fragment pair = channels 8 g .. 8 g + 7 of 32
+        const f32x2 o0 = f32x2{d[0] + bb[fc][0], d[1] + bb[fc][1]}, o1 = f32x2{d[2] + bb[fc][2], d[3] + bb[fc][3]};
+        if (fc & 1) {                                      // (the loop is unrolled: compile-time)
+          if (!(dbg & 128))
+            store8p<SDDM_WT_TILE != 0, T>((char*)out, ors, (unsigned)(po + n0 + cw0 + (fc / 2) * 32 + 8 * g) * (unsigned)sizeof(T),
+                                          pv0, pv1, o0, o1);
+        } else {
+          pv0 = o0;
+          pv1 = o1;
+        }
+      } else {
+        if (!(dbg & 128)) store4<SDDM_WT_TILE != 0, T>(out + po + co, d[0] + bb[fc][0], d[1] + bb[fc][1], d[2] + bb[fc][2], d[3] + bb[fc][3]);
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {                        // sums about the shift bb (stable)
         s1[fc][i] += d[i];
@@ -370,7 +387,7 @@ __global__ __launch_bounds__(64 * WPX * WCO) void conv_tile_kernel(ConvArgs a) {
       for (int i = 0; i < 4; ++i) {
         const float t1 = row_sum16(s1[fc][i]), t2 = row_sum16(s2[fc][i]);
         if (c16 == 0) {
-          float* e = red + (wp * NB + cw0 + fc * 16 + 4 * g + i) * 3;
+          float* e = red + (wp * NB + cw0 + slab_channel<ST16>(fc * 16 + 4 * g + i)) * 3;
           e[0] = nr; e[1] = t1; e[2] = t2;
         }
       }

@@ -150,18 +150,22 @@ __global__ __launch_bounds__(256) void conv_in_kernel(ConvInArgs a) {
   // bias and weights first: issued before the frame image loads, so their round trip overlaps
   // the image's instead of following it (stamps: the staging phase was two round trips, 4.5 us)
   constexpr int KPL = sizeof(T) == 4 ? 5 : 8;   // K values per lane per pixel fragment
+  // 16-bit storage with SDDM_ST16_IN: MFMA row r of fragment fc computes channel pair_channel(fc, r),
+  // so the lane's two accumulators are channels 8 g .. 8 g + 7 (one 16-byte store per pixel)
+  constexpr bool ST16 = SDDM_ST16_IN != 0 && sizeof(T) == 2;
+  auto chan = [](int fc, int r) { return ST16 ? pair_channel(fc, r) : fc * 16 + r; };
   float bias[2][4];
 #pragma unroll
   for (int fc = 0; fc < 2; ++fc)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) bias[fc][i] = a.bias[fc * 16 + 4 * g + i];
+    for (int i = 0; i < 4; ++i) bias[fc][i] = a.bias[chan(fc, 4 * g + i)];
   float wf[2][KPL];                             // weights as MFMA A operands (rows = output channels)
 #pragma unroll
   for (int j = 0; j < KPL; ++j) {
     const int k = sizeof(T) == 4 ? 4 * j + g : 8 * g + j;
     const int kk = k < 18 ? k : 0;              // (clamped: unconditional loads, masked below)
 #pragma unroll
-    for (int fc = 0; fc < 2; ++fc) wf[fc][j] = a.w[(fc * 16 + (lane & 15)) * 18 + kk];
+    for (int fc = 0; fc < 2; ++fc) wf[fc][j] = a.w[chan(fc, lane & 15) * 18 + kk];
   }
   {  // every load of the frame image issued before the first is stored (clamped addresses:
      // a load under a condition is waited for at the branch join)
@@ -217,6 +221,8 @@ __global__ __launch_bounds__(256) void conv_in_kernel(ConvInArgs a) {
       bp[fc][h] = f32x2{bias[fc][2 * h], bias[fc][2 * h + 1]};
     }
   const float rW = 1.0f / (float)W;
+  T* const oimg = (T*)a.out + (size_t)b * F * W * CO;     // this block's output image
+  [[maybe_unused]] const __amdgpu_buffer_rsrc_t ors = out_rsrc(oimg, (unsigned)(F * W * CO) * (unsigned)sizeof(T));
   __syncthreads();                                        // frame image staged
   SDDM_STAMP_AT(a, 1, blockIdx.x + blockIdx.y * (a.F / a.TR));
   const float* imgf = &img[0][0];
@@ -259,6 +265,7 @@ __global__ __launch_bounds__(256) void conv_in_kernel(ConvInArgs a) {
       }
     }
     T* op = (T*)a.out + (((size_t)b * F + f0 + r) * W + w) * CO;
+    f32x2 ov[2][2];
 #pragma unroll
     for (int fc = 0; fc < 2; ++fc) {
       // statistics of the fp32 values about the shift = bias (common to the whole tile)
@@ -267,8 +274,13 @@ __global__ __launch_bounds__(256) void conv_in_kernel(ConvInArgs a) {
       st1[fc][1] += d1;
       st2[fc][0] = __builtin_elementwise_fma(d0, d0, st2[fc][0]);
       st2[fc][1] = __builtin_elementwise_fma(d1, d1, st2[fc][1]);
-      store4p<T>(op + fc * 16 + 4 * g, d0 + bp[fc][0], d1 + bp[fc][1]);
+      ov[fc][0] = d0 + bp[fc][0];
+      ov[fc][1] = d1 + bp[fc][1];
+      if constexpr (!ST16) store4p<SDDM_WT_IN != 0, T>(op + fc * 16 + 4 * g, ov[fc][0], ov[fc][1]);
     }
+    if constexpr (ST16)
+      store8p<SDDM_WT_IN != 0, T>((char*)oimg, ors, (unsigned)(((f0 + r) * W + w) * CO + 8 * g) * (unsigned)sizeof(T),
+                                  ov[0][0], ov[0][1], ov[1][0], ov[1][1]);
   }
   SDDM_STAMP_AT(a, 2, blockIdx.x + blockIdx.y * (a.F / a.TR));
   // tile statistics: lanes of one channel group (xor 1..8) -> 4 waves (LDS), plain sums about the bias
@@ -279,8 +291,8 @@ __global__ __launch_bounds__(256) void conv_in_kernel(ConvInArgs a) {
       const float t1 = row_sum16(st1[fc][i >> 1][i & 1]);    // DPP row adds (VALU)
       const float t2 = row_sum16(st2[fc][i >> 1][i & 1]);
       if ((lane & 15) == 0) {
-        xs_red[wave][fc * 16 + 4 * g + i][0] = t1;
-        xs_red[wave][fc * 16 + 4 * g + i][1] = t2;
+        xs_red[wave][chan(fc, 4 * g + i)][0] = t1;
+        xs_red[wave][chan(fc, 4 * g + i)][1] = t2;
       }
     }
   lds_sync();                                              // (the output stores stay in flight)
