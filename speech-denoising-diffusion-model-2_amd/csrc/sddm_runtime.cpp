@@ -1,11 +1,17 @@
-// libsddm_hip runtime: context, parameter registry, weight packing, per-batch execution plan of
-// one UNetModified2 reverse-diffusion step, and the C ABI declared in include/sddm_hip.h.
+// libsddm_hip runtime: context, parameter registry, weight packer (WeightPacker) and the C ABI
+// declared in include/sddm_hip.h, over four network paths:
+//   UNetModified2        this file: the per-batch plan of one reverse step, run in lanes whose step
+//                        graphs replay concurrently (build_plan, sample_impl)
+//   DiffWave             dw_runtime.h  \
+//   WaveGrad, DenoiseWaveGrad1 / 3  wg_runtime.h   >  sequential networks: each implements SeqNet, and
+//   Waveunet3            wu_runtime.h  /   seq_sample / seq_forward here drive whichever is configured
+// A further sequential network is one such header and one branch on net_type in sddm_configure.
 //
 // Reference counterparts:
 //   sddm_configure      ConfigParser.init_obj('diffusion'|'network'|'arch') (parse_config.py:82-95)
 //   sddm_load_param     model.load_state_dict (infer.py:46-51)
-//   sddm_sample         SDDM.infer (model/model.py:50-124)
-//   sddm_network_forward UNetModified2.forward (model/UNetModified2.py:237-269)
+//   sddm_sample         SDDM.infer (model/model.py:50-124), SDDM_spectrogram.infer (model.py:212-257)
+//   sddm_network_forward the network's forward (e.g. model/UNetModified2.py:237-269)
 //   sddm_transition     GaussianDiffusion.p_transition* (model/diffusion.py:164-223)
 #include <hip/hip_runtime.h>
 
@@ -247,9 +253,32 @@ struct Lane {                         // one row block of the batch: plan + acti
   }
 };
 
-struct DWState;                       // DiffWave path (dw_runtime.h)
-struct WGState;                       // WaveGrad path (wg_runtime.h)
-struct WUState;                       // Waveunet3 path (wu_runtime.h)
+struct sddm_ctx;
+struct WeightPacker;
+
+// A sequential network: its forward is one launch sequence on the caller's stream.  DiffWave
+// (dw_runtime.h), the WaveGrad family (wg_runtime.h) and Waveunet3 (wu_runtime.h) derive from it;
+// seq_sample / seq_forward below drive any of them.  UNetModified2 runs in lanes and graphs instead
+struct SeqNet {
+  std::map<std::string, std::vector<int64_t>> shapes;  // state-dict shapes (set by sddm_configure)
+  std::map<std::string, size_t> woff;                  // packed weights in ctx->warena
+  size_t off_sp = 0, off_rows = 0;                      // StepParams; the path's rows of every t (`pack`)
+  Arena act;                                           // activations of the current (B, N)
+  int B = -1;
+  int64_t N = -1;
+  virtual ~SeqNet() { act.reset(); }
+  // packs the weights; returns the bytes of the path's per-t table (embedding / encoding rows of
+  // t = 0..T), which lands at off_rows
+  virtual size_t pack(sddm_ctx* c, WeightPacker& pk) = 0;
+  // shape checks, then the workspace of (B, N); the same (B, N) again: nothing to do
+  virtual int prepare(sddm_ctx* c, int64_t B, int64_t N) = 0;
+  // step-invariant work of one call at the prepared shape.  noise_level null: the rows of every t
+  // (sampling); otherwise [B]: one row per batch item (a forward)
+  virtual int begin(sddm_ctx* c, const float* cond, const float* noise_level, hipStream_t s) = 0;
+  // one forward: x [B][N] fp32 -> eps().  per_b: the rows of `begin` are per batch item (else row *t_dev)
+  virtual int network(sddm_ctx* c, const float* cond, const float* x, int per_b, int* t_dev, hipStream_t s) = 0;
+  virtual float* eps() = 0;                            // [B][N] fp32 in the workspace
+};
 
 struct sddm_ctx {
   int device = 0, dtype = DT_BF16;
@@ -290,10 +319,7 @@ struct sddm_ctx {
   std::vector<hipEvent_t> ev_pool;
   std::vector<std::pair<int, int>> ev_pend;   // (op index, pool index of the start event)
   std::vector<ProfAcc> op_acc;                // per op index (the same layer list in every lane)
-  // SDDM_spectrogram + DiffWave
-  std::shared_ptr<DWState> dws;
-  std::shared_ptr<WGState> wgs;
-  std::shared_ptr<WUState> wus;
+  std::unique_ptr<SeqNet> seq;                // the network when it is a sequential one, else null
   // measured per-layer kernel tables (sddm_set_conv_tuning), each valid for one lane batch /
   // dtype / num_samples: conv_deep tiles per layer name (pixels per block, waves) and the kernel
   // choice (1 strip, 2 tile (a = configuration), 3 deep (a = pixels, b = waves, c = channels))
@@ -317,107 +343,110 @@ struct sddm_ctx {
 };
 
 // ---------------------------------------------------------------------------------------------
-// weight upload: pack every layer into the kernels' layouts in the compute dtype
+// weight upload: pack every layer into the kernels' layouts in the compute dtype.  WeightPacker
+// (all four networks): host images of the blobs, reserved in the weight arena in the order they are
+// added and copied in one pass once the arena is allocated
 // ---------------------------------------------------------------------------------------------
+struct WeightPacker {
+  struct Blob { size_t off; std::vector<char> bytes; };
+  sddm_ctx* c;
+  std::map<std::string, size_t>& woff;   // blob name -> offset in c->warena
+  std::vector<Blob> blobs;
+  WeightPacker(sddm_ctx* ctx, std::map<std::string, size_t>& offsets) : c(ctx), woff(offsets) {
+    c->warena.reset();
+    woff.clear();
+  }
+  // a zero-filled image of `bytes` bytes that the caller fills with store_elem (the kernel families'
+  // own conv layouts); the pointer holds until finish (a moved vector keeps its buffer)
+  char* raw(const std::string& name, size_t bytes) {
+    Blob b;
+    b.bytes.assign(bytes, 0);
+    b.off = c->warena.reserve(bytes);
+    woff[name] = b.off;
+    blobs.push_back(std::move(b));
+    return blobs.back().bytes.data();
+  }
+  void f32(const std::string& name, const std::vector<float>& v) { std::memcpy(raw(name, v.size() * 4), v.data(), v.size() * 4); }
+  void typed(const std::string& name, const std::vector<float>& v) {   // compute dtype
+    char* p = raw(name, v.size() * dtype_size(c->dtype));
+    for (size_t i = 0; i < v.size(); ++i) store_elem(p, i, v[i], c->dtype);
+  }
+  // after the last blob: the 14 schedule tables, the step parameters (`sp_bytes`) and, if it has
+  // any bytes, one more block of the caller's; allocate, copy the blobs, mark the tables for upload
+  int finish(size_t sp_bytes, size_t* off_sp, size_t more_bytes, size_t* off_more) {
+    Arena& A = c->warena;
+    c->off_tables = A.reserve(sizeof(float) * 14 * (c->T + 1));
+    *off_sp = A.reserve(sp_bytes);
+    if (more_bytes) *off_more = A.reserve(more_bytes);
+    SDDM_HIP_CHECK(A.commit());
+    for (const auto& b : blobs) SDDM_HIP_CHECK(hipMemcpy(A.base + b.off, b.bytes.data(), b.bytes.size(), hipMemcpyHostToDevice));
+    c->params_dirty = false;
+    c->tables_dirty = true;
+    return SDDM_OK;
+  }
+};
+
 static int upload_weights(sddm_ctx* c) {
   const int dt = c->dtype;
   const size_t es = dtype_size(dt);
   auto P = [&](const std::string& k) -> const Param& { return c->params.at(k); };
-  c->warena.reset();
-  c->woff.clear();
   c->temb_off.clear();
-  Arena& A = c->warena;
-  struct Blob { size_t off; std::vector<char> bytes; };
-  std::vector<Blob> blobs;
-  auto add_f32 = [&](const std::string& name, const std::vector<float>& v) {
-    Blob b;
-    b.bytes.resize(v.size() * 4);
-    std::memcpy(b.bytes.data(), v.data(), b.bytes.size());
-    b.off = A.reserve(b.bytes.size());
-    c->woff[name] = b.off;
-    blobs.push_back(std::move(b));
-  };
+  WeightPacker pk(c, c->woff);
+  auto add_f32 = [&](const std::string& name, const std::vector<float>& v) { pk.f32(name, v); };
   // 3x3 conv weight [co][ci][3][3] -> [co_pad64][ci/32][9][32] (T)
   auto add_conv3 = [&](const std::string& name, const Param& w) {
     const int co = (int)w.shape[0], ci = (int)w.shape[1];
     const int cop = (co + 63) / 64 * 64, nch = ci / 32;
-    Blob b;
-    b.bytes.assign((size_t)cop * ci * 9 * es, 0);
+    char* b = pk.raw(name, (size_t)cop * ci * 9 * es);
     for (int o = 0; o < co; ++o)
       for (int i = 0; i < ci; ++i)
         for (int tap = 0; tap < 9; ++tap) {
           const size_t dst = (((size_t)o * nch + i / 32) * 9 + tap) * 32 + (i % 32);
-          store_elem(b.bytes.data(), dst, w.data[((size_t)o * ci + i) * 9 + tap], dt);
+          store_elem(b, dst, w.data[((size_t)o * ci + i) * 9 + tap], dt);
         }
-    b.off = A.reserve(b.bytes.size());
-    c->woff[name] = b.off;
-    blobs.push_back(std::move(b));
     {  // conv_deep fragment image [co/16][ci/32 * 9][64 lanes][8]: lane l of step s holds
        // W[16 cb + (l & 15)][32 (s / 9) + 8 (l >> 4) + j][tap s % 9]
-      Blob bf;
       const int ns = (ci / 32) * 9;
-      bf.bytes.assign((size_t)co * ci * 9 * es, 0);
+      char* bf = pk.raw(name + "_f", (size_t)co * ci * 9 * es);
       for (int o = 0; o < co; ++o)
         for (int i = 0; i < ci; ++i)
           for (int tap = 0; tap < 9; ++tap) {
             const int s = (i / 32) * 9 + tap, l = (o % 16) + 16 * ((i % 32) / 8);
             const size_t dst = (((size_t)(o / 16) * ns + s) * 64 + l) * 8 + i % 8;
-            store_elem(bf.bytes.data(), dst, w.data[((size_t)o * ci + i) * 9 + tap], dt);
+            store_elem(bf, dst, w.data[((size_t)o * ci + i) * 9 + tap], dt);
           }
-      bf.off = A.reserve(bf.bytes.size());
-      c->woff[name + "_f"] = bf.off;
-      blobs.push_back(std::move(bf));
     }
     if (dt != DT_F32) {  // conv_tile image [ci/32][9][4][co][8]: one 16-byte unit = 8 input channels
-      Blob bt;
-      bt.bytes.assign((size_t)co * ci * 9 * es, 0);
+      char* bt = pk.raw(name + "_t", (size_t)co * ci * 9 * es);
       for (int o = 0; o < co; ++o)
         for (int i = 0; i < ci; ++i)
           for (int tap = 0; tap < 9; ++tap) {
             const size_t dst = ((((size_t)(i / 32) * 9 + tap) * 4 + (i % 32) / 8) * co + o) * 8 + i % 8;
-            store_elem(bt.bytes.data(), dst, w.data[((size_t)o * ci + i) * 9 + tap], dt);
+            store_elem(bt, dst, w.data[((size_t)o * ci + i) * 9 + tap], dt);
           }
-      bt.off = A.reserve(bt.bytes.size());
-      c->woff[name + "_t"] = bt.off;
-      blobs.push_back(std::move(bt));
     }
   };
   auto add_conv1 = [&](const std::string& name, const Param& w) {  // [co][ci] -> [co_pad64][ci]
     const int co = (int)w.shape[0], ci = (int)w.shape[1];
     const int cop = (co + 63) / 64 * 64;
-    Blob b;
-    b.bytes.assign((size_t)cop * ci * es, 0);
+    char* b = pk.raw(name, (size_t)cop * ci * es);
     for (int o = 0; o < co; ++o)
-      for (int i = 0; i < ci; ++i) store_elem(b.bytes.data(), (size_t)o * ci + i, w.data[(size_t)o * ci + i], dt);
-    b.off = A.reserve(b.bytes.size());
-    c->woff[name] = b.off;
-    blobs.push_back(std::move(b));
+      for (int i = 0; i < ci; ++i) store_elem(b, (size_t)o * ci + i, w.data[(size_t)o * ci + i], dt);
     {  // conv_deep fragment image [co/16][ci/32][64 lanes][8]
-      Blob bf;
-      bf.bytes.assign((size_t)co * ci * es, 0);
+      char* bf = pk.raw(name + "_f", (size_t)co * ci * es);
       for (int o = 0; o < co; ++o)
         for (int i = 0; i < ci; ++i) {
           const int l = (o % 16) + 16 * ((i % 32) / 8);
-          store_elem(bf.bytes.data(), (((size_t)(o / 16) * (ci / 32) + i / 32) * 64 + l) * 8 + i % 8,
-                     w.data[(size_t)o * ci + i], dt);
+          store_elem(bf, (((size_t)(o / 16) * (ci / 32) + i / 32) * 64 + l) * 8 + i % 8, w.data[(size_t)o * ci + i], dt);
         }
-      bf.off = A.reserve(bf.bytes.size());
-      c->woff[name + "_f"] = bf.off;
-      blobs.push_back(std::move(bf));
     }
     if (dt != DT_F32) {  // conv_tile image [ci/32][4][co][8]
-      Blob bt;
-      bt.bytes.assign((size_t)co * ci * es, 0);
+      char* bt = pk.raw(name + "_t", (size_t)co * ci * es);
       for (int o = 0; o < co; ++o)
         for (int i = 0; i < ci; ++i)
-          store_elem(bt.bytes.data(), (((size_t)(i / 32) * 4 + (i % 32) / 8) * co + o) * 8 + i % 8,
-                     w.data[(size_t)o * ci + i], dt);
-      bt.off = A.reserve(bt.bytes.size());
-      c->woff[name + "_t"] = bt.off;
-      blobs.push_back(std::move(bt));
+          store_elem(bt, (((size_t)(i / 32) * 4 + (i % 32) / 8) * co + o) * 8 + i % 8, w.data[(size_t)o * ci + i], dt);
     }
   };
-  const std::string pfx = "";
   std::vector<float> pw, pb;
   int sc = 0;
   for (const auto& L : unet_layers(c->ucfg, nullptr, nullptr, nullptr)) {
@@ -472,21 +501,72 @@ static int upload_weights(sddm_ctx* c) {
     add_f32("emb_vec", ev);
   }
   c->SC = sc;
-  c->off_tables = A.reserve(sizeof(float) * 14 * (c->T + 1));
-  c->off_tdev = A.reserve(64 * kMaxLanes);
-  c->off_temb_tab = A.reserve(sizeof(float) * (size_t)(c->T + 1) * sc);
-  SDDM_HIP_CHECK(A.commit());
-  for (const auto& b : blobs) SDDM_HIP_CHECK(hipMemcpy(A.base + b.off, b.bytes.data(), b.bytes.size(), hipMemcpyHostToDevice));
-  c->params_dirty = false;
-  c->tables_dirty = true;
   c->plan_B = -1;  // plans hold weight pointers
-  return SDDM_OK;
+  return pk.finish(64 * kMaxLanes, &c->off_tdev, sizeof(float) * (size_t)(c->T + 1) * sc, &c->off_temb_tab);
 }
 
 static int upload_tables(sddm_ctx* c) {
   SDDM_HIP_CHECK(hipMemcpy(c->warena.base + c->off_tables, c->tables.data(), sizeof(float) * c->tables.size(),
                            hipMemcpyHostToDevice));
   c->tables_dirty = false;
+  return SDDM_OK;
+}
+
+#define TRY(x) do { const int _r = (x); if (_r) return _r; } while (0)
+#define TRY_LAUNCH(name, x) do { const hipError_t _e = (x); if (_e != hipSuccess) FAIL(SDDM_ERR_HIP, "%s: %s", name, hipGetErrorString(_e)); } while (0)
+
+// ---------------------------------------------------------------------------------------------
+// sequential networks: weight upload, the reverse loop and the forward of any SeqNet
+// ---------------------------------------------------------------------------------------------
+static int seq_upload_weights(sddm_ctx* c) {
+  SeqNet& n = *c->seq;
+  WeightPacker pk(c, n.woff);
+  const size_t rows_bytes = n.pack(c, pk);
+  n.B = -1;                                            // the next call prepares its workspace anew
+  return pk.finish(64, &n.off_sp, rows_bytes, &n.off_rows);
+}
+
+// The reverse loop.  SDDM_spectrogram.infer (model.py:212-257): cond = spectrogram [B][bins][F],
+// x_T = randn, p_transition 'original' (the context's init / transition modes are those).  SDDM.infer
+// (model.py:50-124): cond = waveform [B][1][N], the initial state and the transition of the
+// context's p_transition.  out [B][1][N]
+static int seq_sample(sddm_ctx* c, const float* cond, int64_t B, int64_t N, uint64_t seed, int64_t row_offset, float* out,
+                      float* record, int sample_inter, const float* noise, hipStream_t s) {
+  SeqNet& n = *c->seq;
+  TRY(n.prepare(c, B, N));
+  TRY(n.begin(c, cond, nullptr, s));
+  const int T = c->T;
+  const float* wave = c->arch_type == "SDDM" ? cond : nullptr;   // the condition as a waveform, or none
+  InitArgs ia{};                                       // x_T (model.py:57-68, 216)
+  ia.mode = c->init_mode; ia.cond = wave; ia.out = out; ia.total = B * N; ia.N = N; ia.T = T;
+  ia.co = c->coef(); ia.seed = seed; ia.row_offset = row_offset; ia.noise = noise;
+  SDDM_HIP_CHECK(launch_init_state(ia, s));
+  StepParams* sp = c->warena.at<StepParams>(n.off_sp);
+  SDDM_HIP_CHECK(launch_set_params(sp, T + 1, seed, row_offset, s));
+  int64_t nrec = 0;
+  for (int t = T; t >= 1; --t) {
+    TRY(n.network(c, cond, out, 0, &sp->t, s));
+    TransArgs ta{};                                    // p_transition* (diffusion.py:164-223)
+    ta.mode = c->tr_mode; ta.x_t = out; ta.eps = n.eps(); ta.cond = wave; ta.out = out;
+    ta.total = B * N; ta.N = N; ta.t = t; ta.t_dev = &sp->t; ta.co = c->coef(); ta.seed = seed; ta.row_offset = row_offset;
+    ta.noise = noise; ta.noise_ld = B * N;
+    SDDM_HIP_CHECK(launch_transition(ta, s));
+    if (record && t % sample_inter == 0) {             // model.py:100-101: keep x_{t-1} when t % inter == 0
+      SDDM_HIP_CHECK(hipMemcpyAsync(record + nrec * B * N, out, sizeof(float) * B * N, hipMemcpyDeviceToDevice, s));
+      ++nrec;
+    }
+  }
+  return SDDM_OK;
+}
+
+// one forward: cond as above, x_t [B][1][N], noise level [B] -> eps [B][1][N]
+static int seq_forward(sddm_ctx* c, const float* cond, const float* x_t, const float* noise_level, int64_t B, int64_t N,
+                       float* eps_out, hipStream_t s) {
+  SeqNet& n = *c->seq;
+  TRY(n.prepare(c, B, N));
+  TRY(n.begin(c, cond, noise_level, s));
+  TRY(n.network(c, cond, x_t, 1, nullptr, s));
+  SDDM_HIP_CHECK(hipMemcpyAsync(eps_out, n.eps(), sizeof(float) * B * N, hipMemcpyDeviceToDevice, s));
   return SDDM_OK;
 }
 
@@ -1097,7 +1177,7 @@ static int ensure_ready(sddm_ctx* c) {
   for (const auto& kv : c->params)
     if (!kv.second.loaded) FAIL(SDDM_ERR_STATE, "parameter %s not loaded", kv.first.c_str());
   if (c->params_dirty) {
-    const int r = c->dws ? dw_upload_weights(c) : (c->wgs ? wg_upload_weights(c) : (c->wus ? wu_upload_weights(c) : upload_weights(c)));
+    const int r = c->seq ? seq_upload_weights(c) : upload_weights(c);
     if (r) return r;
   }
   if (c->tables_dirty) {
@@ -1180,9 +1260,7 @@ void sddm_destroy(sddm_ctx* c) {
     if (c->ev_done[k]) (void)hipEventDestroy(c->ev_done[k]);
   }
   c->lanes.clear();
-  if (c->dws) c->dws->act.reset();
-  if (c->wgs) c->wgs->act.reset();
-  if (c->wus) c->wus->act.reset();
+  c->seq.reset();
   if (c->ev_in) (void)hipEventDestroy(c->ev_in);
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
   c->warena.reset();
@@ -1193,6 +1271,26 @@ int sddm_schedule(const char* schedule, int n_timestep, double linear_start, dou
   if (!schedule || !out || n_timestep < 1) FAIL(SDDM_ERR_INVALID_ARG, "bad schedule arguments");
   if (compute_schedule(schedule, n_timestep, linear_start, linear_end, out))
     FAIL(SDDM_ERR_NOT_IMPLEMENTED, "schedule '%s'", schedule);
+  return SDDM_OK;
+}
+
+// the common ending of sddm_configure: the schedule, the parameter registry of `shapes` (all
+// unloaded), the sequential network (null: UNetModified2 or none) and a weight arena to be rebuilt
+static int finish_configure(sddm_ctx* c, int T, std::vector<float>& tabs, const std::map<std::string, std::vector<int64_t>>& shapes,
+                            std::unique_ptr<SeqNet> seq, int num_samples) {
+  c->T = T;
+  c->tables.swap(tabs);
+  c->tables_dirty = true;
+  c->num_samples = num_samples;
+  c->params.clear();
+  for (const auto& kv : shapes) c->params[kv.first].shape = kv.second;
+  c->seq = std::move(seq);
+  if (c->seq) c->seq->shapes = shapes;
+  c->params_dirty = true;
+  c->plan_B = -1;
+  c->lanes.clear();
+  c->warena.reset();
+  c->configured = true;
   return SDDM_OK;
 }
 
@@ -1253,21 +1351,12 @@ int sddm_configure(sddm_ctx* c, const char* json) {
   std::vector<float> tabs((size_t)14 * (T + 1));
   if (compute_schedule(sched, T, ls, le, tabs.data())) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "schedule '%s' (diffusion.py:84)", sched.c_str());
   c->net_type = net.string("type", "");
-  if (c->net_type.empty()) {  // diffusion-only context: transitions / initial state
-    c->T = T;
-    c->tables.swap(tabs);
-    c->tables_dirty = true;
-    c->params.clear();
-    c->plan_B = -1;
-    c->lanes.clear();
-    c->warena.reset();
-    c->configured = true;
-    return SDDM_OK;
-  }
+  if (c->net_type.empty())    // diffusion-only context: transitions / initial state
+    return finish_configure(c, T, tabs, {}, nullptr, c->num_samples);
   if (c->net_type == "DiffWave") {                               // diffwave.py:113-131
     if (c->arch_type != "SDDM_spectrogram") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "DiffWave needs arch SDDM_spectrogram");
     const Json& na = net.at("args");
-    auto d = std::make_shared<DWState>();
+    auto d = std::make_unique<DWState>();
     d->C = (int)na.number("residual_channels", 64);
     d->L = (int)na.number("residual_layers", 30);
     d->cycle = (int)na.number("dilation_cycle_length", 10);
@@ -1277,25 +1366,9 @@ int sddm_configure(sddm_ctx* c, const char* json) {
     if (d->C != 64) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "DiffWave residual_channels %d (kernels are built for 64)", d->C);
     if (d->L < 1 || d->cycle < 1 || d->bins < 1) FAIL(SDDM_ERR_INVALID_ARG, "DiffWave geometry");
     if (d->hop != 256) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "hop_samples %d: SpectrogramUpsampler upsamples x256", d->hop);
-    c->T = T;
-    c->tables.swap(tabs);
-    c->tables_dirty = true;
-    c->num_samples = -1;
-    c->params.clear();
-    for (const auto& kv : dw_param_shapes(*d)) {
-      Param p;
-      p.shape = kv.second;
-      c->params[kv.first] = p;
-    }
+    const auto shapes = dw_param_shapes(*d);
+    finish_configure(c, T, tabs, shapes, std::move(d), -1);
     c->params["diffusion_embedding.embedding_vector"].loaded = true;   // optional (default computed)
-    c->dws = d;
-    c->wgs.reset();
-    c->wus.reset();
-    c->params_dirty = true;
-    c->plan_B = -1;
-    c->lanes.clear();
-    c->warena.reset();
-    c->configured = true;
     return SDDM_OK;
   }
   if (const wg::Variant* wv = wg::find_variant(c->net_type)) {   // wavegrad.py:140-179, 184-242, 307-353
@@ -1307,60 +1380,20 @@ int sddm_configure(sddm_ctx* c, const char* json) {
       if (c->arch_type != "SDDM") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "%s needs arch SDDM (its condition is a waveform)", wv->name);
       c->hop_samples = wv->hop;
     }
-    c->T = T;
-    c->tables.swap(tabs);
-    c->tables_dirty = true;
-    c->num_samples = -1;
-    c->params.clear();
-    auto ws = std::make_shared<WGState>();
+    auto ws = std::make_unique<WGState>();
     ws->v = wv;
-    ws->shapes = wg_param_shapes(*wv);
-    for (const auto& kv : ws->shapes) {
-      Param p;
-      p.shape = kv.second;
-      c->params[kv.first] = p;
-    }
-    c->dws.reset();
-    c->wgs = ws;
-    c->wus.reset();
-    c->params_dirty = true;
-    c->plan_B = -1;
-    c->lanes.clear();
-    c->warena.reset();
-    c->configured = true;
-    return SDDM_OK;
+    return finish_configure(c, T, tabs, wg_param_shapes(*wv), std::move(ws), -1);
   }
   if (c->net_type == "Waveunet3") {                              // waveunet3.py:314-416, config_waveunet3.json
     if (c->arch_type != "SDDM") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "Waveunet3 needs arch SDDM (its condition is a waveform)");
     const int r = wu_check_config(net.at("args"));
     if (r) return r;
-    c->T = T;
-    c->tables.swap(tabs);
-    c->tables_dirty = true;
-    c->num_samples = -1;
-    c->params.clear();
-    auto us = std::make_shared<WUState>();
-    us->shapes = wu_param_shapes(us->net);
-    for (const auto& kv : us->shapes) {
-      Param p;
-      p.shape = kv.second;
-      c->params[kv.first] = p;
-    }
-    c->dws.reset();
-    c->wgs.reset();
-    c->wus = us;
-    c->params_dirty = true;
-    c->plan_B = -1;
-    c->lanes.clear();
-    c->warena.reset();
-    c->configured = true;
-    return SDDM_OK;
+    auto us = std::make_unique<WUState>();
+    const auto shapes = wu_param_shapes(us->net);
+    return finish_configure(c, T, tabs, shapes, std::move(us), -1);
   }
   if (c->net_type != "UNetModified2") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "network type '%s'", c->net_type.c_str());
   if (c->arch_type != "SDDM") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "UNetModified2 under arch '%s'", c->arch_type.c_str());
-  c->dws.reset();
-  c->wgs.reset();
-  c->wus.reset();
   const Json& na = net.at("args");
   UNetCfg u;
   u.in_channel = (int)na.number("in_channel", 2);
@@ -1381,23 +1414,8 @@ int sddm_configure(sddm_ctx* c, const char* json) {
   const int div = 1 << (int)u.mults.size();
   if (F % div || u.seg % div) FAIL(SDDM_ERR_SHAPE, "n_frames %d and segment_len %d must be multiples of %d", F, u.seg, div);
   if (u.seg % u.stride) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "segment_len %% segment_stride != 0");
-  c->T = T;
-  c->tables.swap(tabs);
-  c->tables_dirty = true;
   c->ucfg = u;
-  c->num_samples = Ns;
-  c->params.clear();
-  for (const auto& kv : unet_param_shapes(u)) {
-    Param p;
-    p.shape = kv.second;
-    c->params[kv.first] = p;
-  }
-  c->params_dirty = true;
-  c->plan_B = -1;
-  c->lanes.clear();
-  c->warena.reset();
-  c->configured = true;
-  return SDDM_OK;
+  return finish_configure(c, T, tabs, unet_param_shapes(u), nullptr, Ns);
 }
 
 int sddm_load_param(sddm_ctx* c, const char* key_c, const void* host_ptr, const int64_t* shape, int ndim,
@@ -1491,9 +1509,7 @@ static int sample_impl(sddm_ctx* c, const float* cond, int64_t B, int64_t N, uin
   int r = ensure_ready(c);
   if (r) return r;
   if (!cond || !out) FAIL(SDDM_ERR_INVALID_ARG, "NULL tensor");
-  if (c->dws) return dw_sample(c, cond, B, N, seed, row_offset, out, record, sample_inter, noise, (hipStream_t)stream);
-  if (c->wgs) return wg_sample(c, cond, B, N, seed, row_offset, out, record, sample_inter, noise, (hipStream_t)stream);
-  if (c->wus) return wu_sample(c, cond, B, N, seed, row_offset, out, record, sample_inter, noise, (hipStream_t)stream);
+  if (c->seq) return seq_sample(c, cond, B, N, seed, row_offset, out, record, sample_inter, noise, (hipStream_t)stream);
   r = prepare_plan(c, B, N);
   if (r) return r;
   hipStream_t user = (hipStream_t)stream;
@@ -1603,9 +1619,7 @@ int sddm_network_forward(sddm_ctx* c, const float* cond, const float* x_t, const
   int r = ensure_ready(c);
   if (r) return r;
   if (!cond || !x_t || !noise_level || !eps_out) FAIL(SDDM_ERR_INVALID_ARG, "NULL tensor");
-  if (c->dws) return dw_forward(c, cond, x_t, noise_level, B, N, eps_out, (hipStream_t)stream);
-  if (c->wgs) return wg_forward(c, cond, x_t, noise_level, B, N, eps_out, (hipStream_t)stream);
-  if (c->wus) return wu_forward(c, cond, x_t, noise_level, B, N, eps_out, (hipStream_t)stream);
+  if (c->seq) return seq_forward(c, cond, x_t, noise_level, B, N, eps_out, (hipStream_t)stream);
   r = prepare_plan(c, B, N);
   if (r) return r;
   hipStream_t s = (hipStream_t)stream;

@@ -1,6 +1,7 @@
-// WaveGrad-family path of the runtime (included by sddm_runtime.cpp after sddm_ctx): configuration,
-// weight packing, workspace and the sampling loops of three networks of reference model/wavegrad.py,
-// described by one table each (wg::Variant) and run by the same kernels (wavegrad.hip):
+// WaveGrad-family path of the runtime (included by sddm_runtime.cpp after sddm_ctx and SeqNet):
+// weight packing, workspace and forward of three networks of reference model/wavegrad.py as one
+// SeqNet, described by one table each (wg::Variant) and run by the same kernels (wavegrad.hip);
+// seq_sample runs the reverse loop over them:
 //
 //   WaveGrad          (wavegrad.py:140-179) under SDDM_spectrogram.infer (model.py:212-257)
 //   DenoiseWaveGrad1  (wavegrad.py:184-242) under SDDM.infer (model.py:50-124), waveform condition
@@ -71,15 +72,22 @@ static const Variant* find_variant(const std::string& name) {
 }
 }  // namespace wg
 
-struct WGState {
+struct WGConvSpec;
+struct WGState : SeqNet {                             // shapes: wg_param_shapes of the variant
   static constexpr int kSpecC = 128;                  // WaveGrad's first_conv input channels
   const wg::Variant* v = &wg::kVariants[0];           // the context's network (set by sddm_configure)
-  std::map<std::string, std::vector<int64_t>> shapes; // its state-dict shapes (wg_param_shapes)
-  std::map<std::string, size_t> woff;                 // packed weights in ctx->warena
-  size_t off_tables = 0, off_sp = 0, off_enctab = 0, off_ev = 0;
-  Arena act;                                          // activations of the current (B, F)
-  std::map<std::string, size_t> aoff;
-  int B = -1, F = -1;
+  std::map<std::string, size_t> aoff;                 // activation buffers in act
+  int F = -1;                                         // bottom positions of the current (B, N): N = hop F
+  const float* enc = nullptr;                         // the encoding rows of the current call (begin)
+  size_t pack(sddm_ctx* c, WeightPacker& pk) override;
+  int prepare(sddm_ctx* c, int64_t B, int64_t N) override;
+  int begin(sddm_ctx* c, const float* cond, const float* noise_level, hipStream_t s) override;
+  int network(sddm_ctx* c, const float* cond, const float* audio, int enc_per_b, int* t_dev, hipStream_t s) override;
+  float* eps() override { return act.at<float>(aoff.at("eps")); }
+  int conv(sddm_ctx* c, WGConvSpec q, int B, const float* enc, int enc_per_b, const int* t_dev, hipStream_t s);
+  int dblock(sddm_ctx* c, const std::string& p, const char* xs, int64_t lin, const wg::Down& dn, int64_t lout,
+             const std::string& o, const char* out, int B, hipStream_t s);
+  int up0_head(sddm_ctx* c, int B, const int64_t* L, hipStream_t s);
 };
 
 // state-dict shapes of a variant (wavegrad.py:140-165, 189-224, 312-339) without the
@@ -122,23 +130,11 @@ static std::map<std::string, std::vector<int64_t>> wg_param_shapes(const wg::Var
   return s;
 }
 
-static int wg_upload_weights(sddm_ctx* c) {
-  WGState& d = *c->wgs;
+size_t WGState::pack(sddm_ctx* c, WeightPacker& pk) {
+  const WGState& d = *this;
   const int dt = c->dtype;
   const size_t es = dtype_size(dt);
-  c->warena.reset();
-  d.woff.clear();
-  Arena& A = c->warena;
-  struct Blob { size_t off; std::vector<char> bytes; };
-  std::vector<Blob> blobs;
-  auto add_f32 = [&](const std::string& name, const std::vector<float>& v) {
-    Blob b;
-    b.bytes.resize(v.size() * 4);
-    std::memcpy(b.bytes.data(), v.data(), b.bytes.size());
-    b.off = A.reserve(b.bytes.size());
-    d.woff[name] = b.off;
-    blobs.push_back(std::move(b));
-  };
+  auto add_f32 = [&](const std::string& name, const std::vector<float>& v) { pk.f32(name, v); };
   // Conv1d weight [Cout][Cin][K] -> [Cout_pad64][K][Cin] in the compute dtype (zero pad rows)
   const wg::Variant& v = *d.v;
   for (const auto& kv : d.shapes) {
@@ -150,14 +146,10 @@ static int wg_upload_weights(sddm_ctx* c) {
     add_f32(base + ".b", c->params.at(base + ".bias").data);
     if (base == "downsample.0" || base == "downsample_x.0") { add_f32(base + ".w", w); continue; }   // fp32 [32][1 | 2][5], VALU kernels
     const int cop = (co + 63) / 64 * 64;
-    Blob b;
-    b.bytes.assign((size_t)cop * k * ci * es, 0);
+    char* b = pk.raw(base + ".w", (size_t)cop * k * ci * es);
     for (int o = 0; o < co; ++o)
       for (int i = 0; i < ci; ++i)
-        for (int t = 0; t < k; ++t) store_elem(b.bytes.data(), ((size_t)o * k + t) * ci + i, w[((size_t)o * ci + i) * k + t], dt);
-    b.off = A.reserve(b.bytes.size());
-    d.woff[base + ".w"] = b.off;
-    blobs.push_back(std::move(b));
+        for (int t = 0; t < k; ++t) store_elem(b, ((size_t)o * k + t) * ci + i, w[((size_t)o * ci + i) * k + t], dt);
   }
   {  // PositionalEncoding exp vectors, torch fp32 op order (wavegrad.py:45-47)
     std::vector<float> ev;
@@ -170,16 +162,7 @@ static int wg_upload_weights(sddm_ctx* c) {
     }
     add_f32("enc.ev", ev);
   }
-  d.off_tables = A.reserve(sizeof(float) * 14 * (c->T + 1));
-  d.off_sp = A.reserve(64);
-  d.off_enctab = A.reserve(sizeof(float) * (size_t)(c->T + 1) * v.enc_n);
-  c->off_tables = d.off_tables;
-  SDDM_HIP_CHECK(A.commit());
-  for (const auto& b : blobs) SDDM_HIP_CHECK(hipMemcpy(A.base + b.off, b.bytes.data(), b.bytes.size(), hipMemcpyHostToDevice));
-  c->params_dirty = false;
-  c->tables_dirty = true;
-  d.B = -1;
-  return SDDM_OK;
+  return sizeof(float) * (size_t)(c->T + 1) * v.enc_n;   // every t's encoding rows
 }
 
 // lengths of the levels for F bottom positions: L[0] = hop F samples .. L[4]; L[5] = F (upsample.0's input)
@@ -189,16 +172,22 @@ static void wg_lengths(const wg::Variant& v, int F, int64_t* L) {
   L[5] = F;
 }
 
-// activation buffers for (B, F): name -> [B][len][C] in the compute dtype
-static int wg_prepare(sddm_ctx* c, int B, int F) {
-  WGState& d = *c->wgs;
-  if (d.B == B && d.F == F) return SDDM_OK;
+// activation buffers for (B, N): name -> [B][len][C] in the compute dtype
+int WGState::prepare(sddm_ctx* c, int64_t B, int64_t N) {
+  WGState& d = *this;
+  const wg::Variant& v = *d.v;
+  if (B < 1 || B > 65535) FAIL(SDDM_ERR_INVALID_ARG, "batch %lld", (long long)B);
+  if (c->hop_samples != v.hop)
+    FAIL(SDDM_ERR_SHAPE, "hop_samples %d: %s resamples x%d (wavegrad.py:157-163, 217-223, 332-338)", c->hop_samples, v.name, v.hop);
+  if (N < v.hop || N % v.hop)
+    FAIL(SDDM_ERR_SHAPE, "%lld samples is not a positive multiple of %s's hop (%d)", (long long)N, v.name, v.hop);
+  if (d.B == B && d.N == N) return SDDM_OK;
+  const int F = (int)(N / v.hop);
   const size_t es = dtype_size(c->dtype);
   Arena& A = d.act;
   A.reset();
   d.aoff.clear();
   auto buf = [&](const std::string& n, int64_t len, int C) { d.aoff[n] = A.reserve(es * (size_t)B * len * C); };
-  const wg::Variant& v = *d.v;
   int64_t L[6];
   wg_lengths(v, F, L);
   buf("d0", L[0], 32);
@@ -220,7 +209,8 @@ static int wg_prepare(sddm_ctx* c, int B, int F) {
   d.aoff["eps"] = A.reserve(sizeof(float) * (size_t)B * L[0]);
   d.aoff["encb"] = A.reserve(sizeof(float) * (size_t)B * v.enc_n);
   SDDM_HIP_CHECK(A.commit());
-  d.B = B;
+  d.B = (int)B;
+  d.N = N;
   d.F = F;
   return SDDM_OK;
 }
@@ -233,9 +223,8 @@ struct WGConvSpec {
   const char* efilm = nullptr; int post_film = 0; const char* out2 = nullptr;   // WGConvArgs::post_film
 };
 
-static int wg_conv(sddm_ctx* c, WGConvSpec q, int B, const float* enc, int enc_per_b, const int* t_dev,
-                   hipStream_t s) {
-  WGState& d = *c->wgs;
+int WGState::conv(sddm_ctx* c, WGConvSpec q, int B, const float* enc, int enc_per_b, const int* t_dev, hipStream_t s) {
+  WGState& d = *this;
   const Arena& W = c->warena;
   std::string mod;
   WGConvArgs probe{};
@@ -263,53 +252,61 @@ static int wg_conv(sddm_ctx* c, WGConvSpec q, int B, const float* enc, int enc_p
   a.post_film = q.post_film;
   a.efilm = q.efilm ? d.act.base + d.aoff.at(q.efilm) : nullptr;
   a.out2 = q.out2 ? d.act.base + d.aoff.at(q.out2) : nullptr;
-  const hipError_t e = launch_wg_conv(c->dtype, a, s);
-  if (e != hipSuccess) FAIL(SDDM_ERR_HIP, "wg_conv %s: %s", q.w.c_str(), hipGetErrorString(e));
+  TRY_LAUNCH(("wg_conv " + q.w).c_str(), launch_wg_conv(c->dtype, a, s));
   return SDDM_OK;
 }
 
-#define WG_TRY(x) do { const int _r = (x); if (_r) return _r; } while (0)
-
 // DBlock (wavegrad.py:126-137): weights p + {residual_dense, conv.0-2}, input xs [B][lin][dn.ci] ->
 // out [B][lout][dn.co]; scratch buffers o + {r, a, b}
-static int wg_dblock(sddm_ctx* c, const std::string& p, const char* xs, int64_t lin, const wg::Down& dn, int64_t lout,
-                     const std::string& o, const char* out, int B, hipStream_t s) {
-  WG_TRY(wg_conv(c, {xs, lin, dn.ci, WG_MAP_DOWN, dn.f, lout, dn.ci, p + "residual_dense", dn.co, 1, 1, 0, nullptr, 0, 0,
-                     nullptr, 0, 1, 0, (o + "r").c_str()}, B, nullptr, 0, nullptr, s));
-  WG_TRY(wg_conv(c, {xs, lin, dn.ci, WG_MAP_DOWN, dn.f, lout, dn.ci, p + "conv.0", dn.co, 3, 1, 1, nullptr, 0, 0,
-                     nullptr, 0, 1, 0, (o + "a").c_str()}, B, nullptr, 0, nullptr, s));
-  WG_TRY(wg_conv(c, {(o + "a").c_str(), lout, dn.co, WG_MAP_ID, 1, lout, dn.co, p + "conv.1", dn.co, 3, 2, 1, nullptr, 0, 0,
-                     nullptr, 0, 1, 0, (o + "b").c_str()}, B, nullptr, 0, nullptr, s));
-  WG_TRY(wg_conv(c, {(o + "b").c_str(), lout, dn.co, WG_MAP_ID, 1, lout, dn.co, p + "conv.2", dn.co, 3, 4, 1, nullptr, 0, 0,
-                     (o + "r").c_str(), WG_MAP_ID, 1, lout, out}, B, nullptr, 0, nullptr, s));
+int WGState::dblock(sddm_ctx* c, const std::string& p, const char* xs, int64_t lin, const wg::Down& dn, int64_t lout,
+                    const std::string& o, const char* out, int B, hipStream_t s) {
+  TRY(conv(c, {xs, lin, dn.ci, WG_MAP_DOWN, dn.f, lout, dn.ci, p + "residual_dense", dn.co, 1, 1, 0, nullptr, 0, 0,
+               nullptr, 0, 1, 0, (o + "r").c_str()}, B, nullptr, 0, nullptr, s));
+  TRY(conv(c, {xs, lin, dn.ci, WG_MAP_DOWN, dn.f, lout, dn.ci, p + "conv.0", dn.co, 3, 1, 1, nullptr, 0, 0,
+               nullptr, 0, 1, 0, (o + "a").c_str()}, B, nullptr, 0, nullptr, s));
+  TRY(conv(c, {(o + "a").c_str(), lout, dn.co, WG_MAP_ID, 1, lout, dn.co, p + "conv.1", dn.co, 3, 2, 1, nullptr, 0, 0,
+               nullptr, 0, 1, 0, (o + "b").c_str()}, B, nullptr, 0, nullptr, s));
+  TRY(conv(c, {(o + "b").c_str(), lout, dn.co, WG_MAP_ID, 1, lout, dn.co, p + "conv.2", dn.co, 3, 4, 1, nullptr, 0, 0,
+               (o + "r").c_str(), WG_MAP_ID, 1, lout, out}, B, nullptr, 0, nullptr, s));
   return SDDM_OK;
 }
 
 // upsample.0's block1 / block2[0] from "uin" (wavegrad.py:92-97): no FiLM reaches them
-static int wg_up0_head(sddm_ctx* c, int B, const int64_t* L, hipStream_t s) {
-  const wg::Up& u = c->wgs->v->up[0];
-  WG_TRY(wg_conv(c, {"uin", L[5], u.ci, WG_MAP_ID, 1, L[5], u.ci, "upsample.0.block1", u.h, 1, 1, 0, nullptr, 0, 0, nullptr, 0, 1, 0, "u0b1"},
-                 B, nullptr, 0, nullptr, s));
-  WG_TRY(wg_conv(c, {"uin", L[5], u.ci, WG_MAP_UP, u.f, L[4], u.ci, "upsample.0.block2.0", u.h, 3, u.dil[0], 1, nullptr, 0, 0,
-                     nullptr, 0, 1, 0, "u0y0"}, B, nullptr, 0, nullptr, s));
+int WGState::up0_head(sddm_ctx* c, int B, const int64_t* L, hipStream_t s) {
+  const wg::Up& u = v->up[0];
+  TRY(conv(c, {"uin", L[5], u.ci, WG_MAP_ID, 1, L[5], u.ci, "upsample.0.block1", u.h, 1, 1, 0, nullptr, 0, 0, nullptr, 0, 1, 0, "u0b1"},
+           B, nullptr, 0, nullptr, s));
+  TRY(conv(c, {"uin", L[5], u.ci, WG_MAP_UP, u.f, L[4], u.ci, "upsample.0.block2.0", u.h, 3, u.dil[0], 1, nullptr, 0, 0,
+               nullptr, 0, 1, 0, "u0y0"}, B, nullptr, 0, nullptr, s));
   return SDDM_OK;
 }
 
-// step-invariant work of one call.  WaveGrad: cond = spectrogram [B][128][F] -> first_conv
+// step-invariant work of one call.  All: the PositionalEncoding rows, of every t (sampling) or one
+// per batch item (a forward).  WaveGrad: cond = spectrogram [B][128][F] -> first_conv
 // (wavegrad.py:175).  DenoiseWaveGrad1: cond = waveform [B][N] -> downsample_x (wavegrad.py:234-236;
 // its levels 1-4 borrow the y_t branch's buffers, which the steps overwrite afterwards).  Both then
-// run upsample.0's block1 / block2[0].  DenoiseWaveGrad3 has no step-invariant work
-static int wg_condition(sddm_ctx* c, const float* cond, int B, int F, hipStream_t s) {
-  WGState& d = *c->wgs;
+// run upsample.0's block1 / block2[0].  DenoiseWaveGrad3 has no more step-invariant work
+int WGState::begin(sddm_ctx* c, const float* cond, const float* noise_level, hipStream_t s) {
+  WGState& d = *this;
   const wg::Variant& v = *d.v;
+  float* rows = noise_level ? d.act.at<float>(d.aoff.at("encb")) : c->warena.at<float>(d.off_rows);
+  WGEncArgs e{};
+  e.noise_levels = noise_level; e.table = c->dtab(3);
+  e.time_step_mode = c->noise_time_step; e.R = noise_level ? d.B : c->T + 1;
+  e.ev = c->warena.at<float>(d.woff.at("enc.ev")); e.stride = v.enc_n; e.n = v.enc_n;
+  for (int i = 0; i < 5; ++i) { e.dims[i] = v.film[i].ci; e.offs[i] = v.enc_off[i]; }
+  e.out = rows;
+  SDDM_HIP_CHECK(launch_wg_enc(e, s));
+  d.enc = rows;
   if (!v.hoist) return SDDM_OK;
+  const int B = d.B, F = d.F;
   int64_t L[6];
   wg_lengths(v, F, L);
   if (v.kind == wg::kWaveGrad) {
     WGSpecArgs sa{cond, d.act.base + d.aoff.at("spec"), B, WGState::kSpecC, F};
     SDDM_HIP_CHECK(launch_wg_spec(c->dtype, sa, s));
-    WG_TRY(wg_conv(c, {"spec", L[5], 128, WG_MAP_ID, 1, L[5], 128, "first_conv", v.up[0].ci, 3, 1, 0, nullptr, 0, 0, nullptr, 0, 1, 0, "uin"},
-                   B, nullptr, 0, nullptr, s));
+    TRY(conv(c, {"spec", L[5], 128, WG_MAP_ID, 1, L[5], 128, "first_conv", v.up[0].ci, 3, 1, 0, nullptr, 0, 0, nullptr, 0, 1, 0, "uin"},
+             B, nullptr, 0, nullptr, s));
   } else {
     const Arena& W = c->warena;
     WGFirstArgs fa{cond, W.at<float>(d.woff.at("downsample_x.0.w")), W.at<float>(d.woff.at("downsample_x.0.b")),
@@ -318,20 +315,20 @@ static int wg_condition(sddm_ctx* c, const float* cond, int B, int F, hipStream_
     std::string x = "d0";
     for (int i = 1; i < 5; ++i) {
       const std::string si = std::to_string(i), o = "d" + si;
-      WG_TRY(wg_dblock(c, "downsample_x." + si + ".", x.c_str(), L[i - 1], v.down[i], L[i], o, o.c_str(), B, s));
+      TRY(dblock(c, "downsample_x." + si + ".", x.c_str(), L[i - 1], v.down[i], L[i], o, o.c_str(), B, s));
       x = o;
     }
-    WG_TRY(wg_dblock(c, v.bottom_key, x.c_str(), L[4], v.bottom, L[5], "bn", "uin", B, s));
+    TRY(dblock(c, v.bottom_key, x.c_str(), L[4], v.bottom, L[5], "bn", "uin", B, s));
   }
-  return wg_up0_head(c, B, L, s);
+  return up0_head(c, B, L, s);
 }
 
-// one forward of the y_t branch and the decoder: audio [B][N] fp32 (and, for DenoiseWaveGrad3, the
-// condition waveform [B][N]) -> eps [B][N] fp32 (aoff "eps")
-static int wg_network(sddm_ctx* c, const float* cond, const float* audio, int B, int F, const float* enc, int enc_per_b,
-                      int* t_dev, hipStream_t s) {
-  WGState& d = *c->wgs;
+// one forward of the y_t branch and the decoder (wavegrad.py:167-179, 226-242, 341-353): audio
+// [B][N] fp32 (and, for DenoiseWaveGrad3, the condition waveform [B][N]) -> eps [B][N] fp32 (aoff "eps")
+int WGState::network(sddm_ctx* c, const float* cond, const float* audio, int enc_per_b, int* t_dev, hipStream_t s) {
+  WGState& d = *this;
   const wg::Variant& v = *d.v;
+  const int B = d.B, F = d.F;
   const Arena& W = c->warena;
   int64_t L[6];
   wg_lengths(v, F, L);
@@ -349,18 +346,18 @@ static int wg_network(sddm_ctx* c, const float* cond, const float* audio, int B,
     const std::string si = std::to_string(i);
     if (i > 0) {
       const std::string o = "d" + si;
-      WG_TRY(wg_dblock(c, "downsample." + si + ".", x.c_str(), L[i - 1], v.down[i], L[i], o, o.c_str(), B, s));
+      TRY(dblock(c, "downsample." + si + ".", x.c_str(), L[i - 1], v.down[i], L[i], o, o.c_str(), B, s));
       x = o;
     }
     const wg::Film& fm = v.film[i];                      // FiLM (wavegrad.py:66-71)
     const std::string p = "film." + si + ".", o = "f" + si;
-    WG_TRY(wg_conv(c, {x.c_str(), L[i], fm.ci, WG_MAP_ID, 1, L[i], fm.ci, p + "input_conv", fm.ci, 3, 1, 0, nullptr, 1,
-                       v.enc_off[i], nullptr, 0, 1, 0, (o + "a").c_str()}, B, enc, enc_per_b, t_dev, s));
-    WG_TRY(wg_conv(c, {(o + "a").c_str(), L[i], fm.ci, WG_MAP_ID, 1, L[i], fm.ci, p + "output_conv", 2 * fm.co, 3, 1, 0, nullptr,
-                       0, 0, nullptr, 0, 1, 0, o.c_str()}, B, enc, enc_per_b, t_dev, s));
+    TRY(conv(c, {x.c_str(), L[i], fm.ci, WG_MAP_ID, 1, L[i], fm.ci, p + "input_conv", fm.ci, 3, 1, 0, nullptr, 1,
+                 v.enc_off[i], nullptr, 0, 1, 0, (o + "a").c_str()}, B, enc, enc_per_b, t_dev, s));
+    TRY(conv(c, {(o + "a").c_str(), L[i], fm.ci, WG_MAP_ID, 1, L[i], fm.ci, p + "output_conv", 2 * fm.co, 3, 1, 0, nullptr,
+                 0, 0, nullptr, 0, 1, 0, o.c_str()}, B, enc, enc_per_b, t_dev, s));
   }
   if (!v.hoist) {                                        // bottleneck (wavegrad.py:349), then upsample.0 in full
-    WG_TRY(wg_dblock(c, v.bottom_key, x.c_str(), L[4], v.bottom, L[5], "bn", "uin", B, s));
+    TRY(dblock(c, v.bottom_key, x.c_str(), L[4], v.bottom, L[5], "bn", "uin", B, s));
   }
   x = "uin";
   for (int i = 0; i < 5; ++i) {                           // UBlock (wavegrad.py:91-112)
@@ -372,110 +369,33 @@ static int wg_network(sddm_ctx* c, const float* cond, const float* audio, int B,
     // block3.1's inputs runs in their producers' epilogues (post_film: y0 holds leaky(film(block2.0
     // out)), m holds leaky(film(x)), z holds leaky(film(block3.0 out))), so shift / scale are read
     // once per element instead of once per 128-channel block of the consumer (upsample.1: 1137 ->
-    // 962 us per step at B=64).  Where upsample.0's block2.0 is step-invariant (wg_condition: WaveGrad,
+    // 962 us per step at B=64).  Where upsample.0's block2.0 is step-invariant (begin: WaveGrad,
     // DenoiseWaveGrad1), its block2.1 keeps the FiLM in the staging (pre 2).  The 128 / 256-channel UBlocks keep the
     // staged FiLM: there the epilogue loads are exposed (all blocks reach their epilogues
     // together) and cost more than the re-reads save (upsample.4: 1324 -> 1675 us)
     const std::string ym = o + "y0", xm = o + "m", xo = o + "x", zo = o + "z", b1 = o + "b1";
     static const int epi_min_h = std::getenv("SDDM_WG_EPI_MIN_H") ? std::atoi(std::getenv("SDDM_WG_EPI_MIN_H")) : 512;
     const bool epi = u.h >= epi_min_h;
-    const bool head_done = i == 0 && v.hoist;            // wg_condition ran block1 / block2[0] (plain, no epilogue FiLM)
+    const bool head_done = i == 0 && v.hoist;            // begin ran block1 / block2[0] (plain, no epilogue FiLM)
     if (!head_done) {
-      WG_TRY(wg_conv(c, {x.c_str(), lin, u.ci, WG_MAP_ID, 1, lin, u.ci, p + "block1", u.h, 1, 1, 0, nullptr, 0, 0, nullptr, 0, 1, 0,
-                         b1.c_str()}, B, enc, enc_per_b, t_dev, s));
-      WG_TRY(wg_conv(c, {x.c_str(), lin, u.ci, WG_MAP_UP, u.f, lout, u.ci, p + "block2.0", u.h, 3, u.dil[0], 1, nullptr, 0, 0,
-                         nullptr, 0, 1, 0, ym.c_str(), epi ? film.c_str() : nullptr, epi ? 1 : 0}, B, enc, enc_per_b, t_dev, s));
+      TRY(conv(c, {x.c_str(), lin, u.ci, WG_MAP_ID, 1, lin, u.ci, p + "block1", u.h, 1, 1, 0, nullptr, 0, 0, nullptr, 0, 1, 0,
+                   b1.c_str()}, B, enc, enc_per_b, t_dev, s));
+      TRY(conv(c, {x.c_str(), lin, u.ci, WG_MAP_UP, u.f, lout, u.ci, p + "block2.0", u.h, 3, u.dil[0], 1, nullptr, 0, 0,
+                   nullptr, 0, 1, 0, ym.c_str(), epi ? film.c_str() : nullptr, epi ? 1 : 0}, B, enc, enc_per_b, t_dev, s));
     }
     const bool pre21 = !epi || head_done;
-    WG_TRY(wg_conv(c, {ym.c_str(), lout, u.h, WG_MAP_ID, 1, lout, u.h, p + "block2.1", u.h, 3, u.dil[1], pre21 ? 2 : 0,
-                       pre21 ? film.c_str() : nullptr, 0, 0, b1.c_str(), WG_MAP_UP, u.f, lin, xo.c_str(),
-                       epi ? film.c_str() : nullptr, epi ? 2 : 0, epi ? xm.c_str() : nullptr}, B, enc, enc_per_b, t_dev, s));
-    WG_TRY(wg_conv(c, {epi ? xm.c_str() : xo.c_str(), lout, u.h, WG_MAP_ID, 1, lout, u.h, p + "block3.0", u.h, 3, u.dil[2],
-                       epi ? 0 : 2, epi ? nullptr : film.c_str(), 0, 0, nullptr, 0, 1, 0, zo.c_str(), epi ? film.c_str() : nullptr,
-                       epi ? 1 : 0}, B, enc, enc_per_b, t_dev, s));
-    WG_TRY(wg_conv(c, {zo.c_str(), lout, u.h, WG_MAP_ID, 1, lout, u.h, p + "block3.1", u.h, 3, u.dil[3], epi ? 0 : 2,
-                       epi ? nullptr : film.c_str(), 0, 0, xo.c_str(), WG_MAP_ID, 1, lout, o.c_str()}, B, enc, enc_per_b, t_dev, s));
+    TRY(conv(c, {ym.c_str(), lout, u.h, WG_MAP_ID, 1, lout, u.h, p + "block2.1", u.h, 3, u.dil[1], pre21 ? 2 : 0,
+                 pre21 ? film.c_str() : nullptr, 0, 0, b1.c_str(), WG_MAP_UP, u.f, lin, xo.c_str(),
+                 epi ? film.c_str() : nullptr, epi ? 2 : 0, epi ? xm.c_str() : nullptr}, B, enc, enc_per_b, t_dev, s));
+    TRY(conv(c, {epi ? xm.c_str() : xo.c_str(), lout, u.h, WG_MAP_ID, 1, lout, u.h, p + "block3.0", u.h, 3, u.dil[2],
+                 epi ? 0 : 2, epi ? nullptr : film.c_str(), 0, 0, nullptr, 0, 1, 0, zo.c_str(), epi ? film.c_str() : nullptr,
+                 epi ? 1 : 0}, B, enc, enc_per_b, t_dev, s));
+    TRY(conv(c, {zo.c_str(), lout, u.h, WG_MAP_ID, 1, lout, u.h, p + "block3.1", u.h, 3, u.dil[3], epi ? 0 : 2,
+                 epi ? nullptr : film.c_str(), 0, 0, xo.c_str(), WG_MAP_ID, 1, lout, o.c_str()}, B, enc, enc_per_b, t_dev, s));
     x = o;
   }
   const int cl = v.up[4].h;
-  WG_TRY(wg_conv(c, {x.c_str(), L[0], cl, WG_MAP_ID, 1, L[0], cl, "last_conv", 1, 3, 1, 0, nullptr, 0, 0, nullptr, 0, 1, 0, "eps"},
-                 B, enc, enc_per_b, t_dev, s));
-  return SDDM_OK;
-}
-
-static int wg_enc(sddm_ctx* c, const float* noise_levels, int rows, float* out, hipStream_t s) {
-  WGState& d = *c->wgs;
-  WGEncArgs e{};
-  e.noise_levels = noise_levels; e.table = c->warena.at<float>(d.off_tables) + (size_t)3 * (c->T + 1);
-  e.time_step_mode = c->noise_time_step; e.R = rows;
-  e.ev = c->warena.at<float>(d.woff.at("enc.ev")); e.stride = d.v->enc_n; e.n = d.v->enc_n;
-  for (int i = 0; i < 5; ++i) { e.dims[i] = d.v->film[i].ci; e.offs[i] = d.v->enc_off[i]; }
-  e.out = out;
-  SDDM_HIP_CHECK(launch_wg_enc(e, s));
-  return SDDM_OK;
-}
-
-static int wg_check_shape(sddm_ctx* c, int64_t B, int64_t N, int* F) {
-  if (B < 1 || B > 65535) FAIL(SDDM_ERR_INVALID_ARG, "batch %lld", (long long)B);
-  const wg::Variant& v = *c->wgs->v;
-  if (c->hop_samples != v.hop)
-    FAIL(SDDM_ERR_SHAPE, "hop_samples %d: %s resamples x%d (wavegrad.py:157-163, 217-223, 332-338)", c->hop_samples, v.name, v.hop);
-  if (N < v.hop || N % v.hop)
-    FAIL(SDDM_ERR_SHAPE, "%lld samples is not a positive multiple of %s's hop (%d)", (long long)N, v.name, v.hop);
-  *F = (int)(N / v.hop);
-  return SDDM_OK;
-}
-
-// The reverse loop over a network of the family.  WaveGrad: SDDM_spectrogram.infer (model.py:212-257),
-// cond = spectrogram [B][128][F], x_T = randn, p_transition 'original' (the context's init / transition
-// modes are those).  DenoiseWaveGrad1 / 3: SDDM.infer (model.py:50-124), cond = waveform [B][1][N], the
-// initial state and the transition of the context's p_transition.  out [B][1][hop F]
-static int wg_sample(sddm_ctx* c, const float* cond, int64_t B, int64_t N, uint64_t seed, int64_t row_offset, float* out,
-                     float* record, int sample_inter, const float* noise, hipStream_t s) {
-  WGState& d = *c->wgs;
-  int F = 0;
-  WG_TRY(wg_check_shape(c, B, N, &F));
-  WG_TRY(wg_prepare(c, (int)B, F));
-  const int T = c->T;
-  const float* wave = d.v->kind == wg::kWaveGrad ? nullptr : cond;   // the condition as a waveform, or none
-  float* enctab = c->warena.at<float>(d.off_enctab);
-  WG_TRY(wg_enc(c, nullptr, T + 1, enctab, s));
-  WG_TRY(wg_condition(c, cond, (int)B, F, s));
-  InitArgs ia{};                                       // x_T (model.py:57-68, 216)
-  ia.mode = c->init_mode; ia.cond = wave; ia.out = out; ia.total = B * N; ia.N = N; ia.T = T;
-  ia.co = c->coef(); ia.seed = seed; ia.row_offset = row_offset; ia.noise = noise;
-  SDDM_HIP_CHECK(launch_init_state(ia, s));
-  StepParams* sp = c->warena.at<StepParams>(d.off_sp);
-  SDDM_HIP_CHECK(launch_set_params(sp, T + 1, seed, row_offset, s));
-  int64_t nrec = 0;
-  float* eps = d.act.at<float>(d.aoff.at("eps"));
-  for (int t = T; t >= 1; --t) {
-    WG_TRY(wg_network(c, wave, out, (int)B, F, enctab, 0, &sp->t, s));
-    TransArgs ta{};                                    // p_transition* (diffusion.py:164-223)
-    ta.mode = c->tr_mode; ta.x_t = out; ta.eps = eps; ta.cond = wave; ta.out = out;
-    ta.total = B * N; ta.N = N; ta.t = t; ta.t_dev = &sp->t; ta.co = c->coef(); ta.seed = seed; ta.row_offset = row_offset;
-    ta.noise = noise; ta.noise_ld = B * N;
-    SDDM_HIP_CHECK(launch_transition(ta, s));
-    if (record && t % sample_inter == 0) {
-      SDDM_HIP_CHECK(hipMemcpyAsync(record + nrec * B * N, out, sizeof(float) * B * N, hipMemcpyDeviceToDevice, s));
-      ++nrec;
-    }
-  }
-  return SDDM_OK;
-}
-
-// one forward (wavegrad.py:167-179, 226-242, 341-353): cond = spectrogram [B][128][F] (WaveGrad) or
-// waveform [B][N] (DenoiseWaveGrad1 / 3), audio [B][N], noise level [B] -> eps [B][N]
-static int wg_forward(sddm_ctx* c, const float* cond, const float* x_t, const float* noise_level, int64_t B, int64_t N,
-                      float* eps_out, hipStream_t s) {
-  WGState& d = *c->wgs;
-  int F = 0;
-  WG_TRY(wg_check_shape(c, B, N, &F));
-  WG_TRY(wg_prepare(c, (int)B, F));
-  float* encb = d.act.at<float>(d.aoff.at("encb"));
-  WG_TRY(wg_enc(c, noise_level, (int)B, encb, s));
-  WG_TRY(wg_condition(c, cond, (int)B, F, s));
-  WG_TRY(wg_network(c, d.v->kind == wg::kWaveGrad ? nullptr : cond, x_t, (int)B, F, encb, 1, nullptr, s));
-  SDDM_HIP_CHECK(hipMemcpyAsync(eps_out, d.act.at<float>(d.aoff.at("eps")), sizeof(float) * B * N, hipMemcpyDeviceToDevice, s));
+  TRY(conv(c, {x.c_str(), L[0], cl, WG_MAP_ID, 1, L[0], cl, "last_conv", 1, 3, 1, 0, nullptr, 0, 0, nullptr, 0, 1, 0, "eps"},
+           B, enc, enc_per_b, t_dev, s));
   return SDDM_OK;
 }

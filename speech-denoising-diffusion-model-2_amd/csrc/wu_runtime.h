@@ -1,6 +1,7 @@
-// Waveunet3 path of the runtime (included by sddm_runtime.cpp after sddm_ctx): configuration,
-// weight packing, workspace and the sampling loop of reference model/waveunet3.py:314-416 at the
-// arguments of config_waveunet3.json, under SDDM.infer (model.py:50-124).  Kernels: waveunet.hip.
+// Waveunet3 path of the runtime (included by sddm_runtime.cpp after sddm_ctx and SeqNet):
+// configuration check, weight packing, workspace and forward of reference model/waveunet3.py:314-416
+// at the arguments of config_waveunet3.json as a SeqNet; seq_sample runs SDDM.infer
+// (model.py:50-124) over it.  Kernels: waveunet.hip.
 //
 // Layers (C = 32 / 64 / 96 / 128, L_i = N / 2^i; every ResnetBlock is block1 -> + noise constant ->
 // block2 -> + res, a Block is GroupNorm -> SiLU -> Conv5):
@@ -59,14 +60,15 @@ static Net build_net() {
 }
 }  // namespace wu
 
-struct WUState {
+struct WUState : SeqNet {
   wu::Net net = wu::build_net();
-  std::map<std::string, std::vector<int64_t>> shapes;
-  std::map<std::string, size_t> woff;                 // packed weights in ctx->warena
-  size_t off_tables = 0, off_sp = 0;
-  Arena act;                                          // activations of the current (B, N)
-  std::map<std::string, size_t> aoff;
-  int B = -1; int64_t N = -1;
+  std::map<std::string, size_t> aoff;                 // activation buffers in act
+  WULevel lv{};                                       // the noise level of the current call (begin)
+  size_t pack(sddm_ctx* c, WeightPacker& pk) override;
+  int prepare(sddm_ctx* c, int64_t B, int64_t N) override;
+  int begin(sddm_ctx* c, const float* cond, const float* noise_level, hipStream_t s) override;
+  int network(sddm_ctx* c, const float* cond, const float* x_t, int per_b, int* t_dev, hipStream_t s) override;
+  float* eps() override { return act.at<float>(aoff.at("eps")); }
 };
 
 // refuses everything the kernels are not instantiated for (the arguments of config_waveunet3.json are)
@@ -110,37 +112,21 @@ static std::map<std::string, std::vector<int64_t>> wu_param_shapes(const wu::Net
   return s;
 }
 
-static int wu_upload_weights(sddm_ctx* c) {
-  WUState& d = *c->wus;
+size_t WUState::pack(sddm_ctx* c, WeightPacker& pk) {
+  const WUState& d = *this;
   const int dt = c->dtype;
   const size_t es = dtype_size(dt);
-  c->warena.reset();
-  d.woff.clear();
-  Arena& A = c->warena;
-  struct Blob { size_t off; std::vector<char> bytes; };
-  std::vector<Blob> blobs;
   auto P = [&](const std::string& k) -> const std::vector<float>& { return c->params.at(k).data; };
-  auto add_f32 = [&](const std::string& name, const std::vector<float>& v) {
-    Blob b;
-    b.bytes.resize(v.size() * 4);
-    std::memcpy(b.bytes.data(), v.data(), b.bytes.size());
-    b.off = A.reserve(b.bytes.size());
-    d.woff[name] = b.off;
-    blobs.push_back(std::move(b));
-  };
+  auto add_f32 = [&](const std::string& name, const std::vector<float>& v) { pk.f32(name, v); };
   // conv weight -> [co][k][ci] in the compute dtype; src index of (o, i, t) given by the caller
   auto add_conv = [&](const std::string& name, int co, int ci, int k, const std::vector<float>& w, bool transposed) {
-    Blob b;
-    b.bytes.assign((size_t)co * k * ci * es, 0);
+    char* b = pk.raw(name, (size_t)co * k * ci * es);
     for (int o = 0; o < co; ++o)
       for (int i = 0; i < ci; ++i)
         for (int t = 0; t < k; ++t) {
           const size_t src = transposed ? ((size_t)i * co + o) * k + t : ((size_t)o * ci + i) * k + t;   // ConvTranspose1d: [ci][co][k]
-          store_elem(b.bytes.data(), ((size_t)o * k + t) * ci + i, w[src], dt);
+          store_elem(b, ((size_t)o * k + t) * ci + i, w[src], dt);
         }
-    b.off = A.reserve(b.bytes.size());
-    d.woff[name] = b.off;
-    blobs.push_back(std::move(b));
   };
   for (const wu::Res& r : d.net.res) {
     const std::string& p = r.p;
@@ -171,27 +157,15 @@ static int wu_upload_weights(sddm_ctx* c) {
   }
   add_f32("out.w", P("waveunet.output_conv.weight"));
   add_f32("out.b", P("waveunet.output_conv.bias"));
-  d.off_tables = A.reserve(sizeof(float) * 14 * (c->T + 1));
-  d.off_sp = A.reserve(64);
-  c->off_tables = d.off_tables;
-  SDDM_HIP_CHECK(A.commit());
-  for (const auto& b : blobs) SDDM_HIP_CHECK(hipMemcpy(A.base + b.off, b.bytes.data(), b.bytes.size(), hipMemcpyHostToDevice));
-  c->params_dirty = false;
-  c->tables_dirty = true;
-  d.B = -1;
-  return SDDM_OK;
-}
-
-static int wu_check_shape(int64_t B, int64_t N) {
-  if (B < 1 || B > 65535) FAIL(SDDM_ERR_INVALID_ARG, "batch %lld", (long long)B);
-  if (N < 8 || N % 8) FAIL(SDDM_ERR_SHAPE, "%lld samples is not a positive multiple of 8 (Waveunet3 halves the length three times)", (long long)N);
-  if (N > (int64_t)1 << 30) FAIL(SDDM_ERR_SHAPE, "%lld samples: Waveunet3 positions are 32-bit", (long long)N);
-  return SDDM_OK;
+  return 0;                                            // no table of its own: the level is one scalar per t
 }
 
 // activation buffers for (B, N): name -> [B][len][C] in the compute dtype
-static int wu_prepare(sddm_ctx* c, int B, int64_t N) {
-  WUState& d = *c->wus;
+int WUState::prepare(sddm_ctx* c, int64_t B, int64_t N) {
+  WUState& d = *this;
+  if (B < 1 || B > 65535) FAIL(SDDM_ERR_INVALID_ARG, "batch %lld", (long long)B);
+  if (N < 8 || N % 8) FAIL(SDDM_ERR_SHAPE, "%lld samples is not a positive multiple of 8 (Waveunet3 halves the length three times)", (long long)N);
+  if (N > (int64_t)1 << 30) FAIL(SDDM_ERR_SHAPE, "%lld samples: Waveunet3 positions are 32-bit", (long long)N);
   if (d.B == B && d.N == N) return SDDM_OK;
   const size_t es = dtype_size(c->dtype);
   Arena& A = d.act;
@@ -220,18 +194,25 @@ static int wu_prepare(sddm_ctx* c, int B, int64_t N) {
   d.aoff["shift"] = A.reserve(sizeof(float) * (size_t)B * 128);
   d.aoff["eps"] = A.reserve(sizeof(float) * (size_t)B * N);
   SDDM_HIP_CHECK(A.commit());
-  d.B = B;
+  d.B = (int)B;
   d.N = N;
   return SDDM_OK;
 }
 
-#define WU_TRY(x) do { const int _r = (x); if (_r) return _r; } while (0)
-#define WU_LAUNCH(name, x) do { const hipError_t _e = (x); if (_e != hipSuccess) FAIL(SDDM_ERR_HIP, "%s: %s", name, hipGetErrorString(_e)); } while (0)
+// the noise level the ResnetBlocks add: sqrt_alpha_bar[t] or t of the step counter (sampling,
+// model.py:84-89) or the caller's [B] (a forward).  No launch
+int WUState::begin(sddm_ctx* c, const float*, const float* noise_level, hipStream_t) {
+  if (noise_level) lv = WULevel{noise_level, nullptr, 0, nullptr};
+  else lv = WULevel{nullptr, c->dtab(3), c->noise_time_step, &c->warena.at<StepParams>(off_sp)->t};
+  return SDDM_OK;
+}
 
-// one forward (waveunet3.py:383-416): cond, x_t [B][N] fp32 -> eps [B][N] fp32 (aoff "eps")
-static int wu_network(sddm_ctx* c, const float* cond, const float* x_t, int B, int64_t N, WULevel lv, int* t_dev, hipStream_t s) {
-  WUState& d = *c->wus;
+// one forward (waveunet3.py:383-416): cond, x_t [B][N] fp32 -> clamp(output_conv) = eps [B][N] fp32 (aoff "eps")
+int WUState::network(sddm_ctx* c, const float* cond, const float* x_t, int, int* t_dev, hipStream_t s) {
+  WUState& d = *this;
   const Arena& W = c->warena;
+  const int B = d.B;
+  const int64_t N = d.N;
   const int dt = c->dtype;
   auto act = [&](const std::string& n) -> char* { return d.act.base + d.aoff.at(n); };
   auto wf = [&](const std::string& n) -> const float* { return W.at<float>(d.woff.at(n)); };
@@ -242,7 +223,7 @@ static int wu_network(sddm_ctx* c, const float* cond, const float* x_t, int B, i
   // scale / shift of GroupNorm(G, C) with the named affine over the latest producer's [B][L][C]
   auto finalize = [&](int C, int G, int64_t L, const std::string& gamma, const std::string& beta) -> int {
     WUGnArgs g{stats, cur_slots, C, G, L, wf(gamma), wf(beta), 1e-5f, scale, shift, B};
-    WU_LAUNCH("wu_gn_finalize", launch_wu_gn_finalize(g, s));
+    TRY_LAUNCH("wu_gn_finalize", launch_wu_gn_finalize(g, s));
     return SDDM_OK;
   };
   const char* x = nullptr;                             // the running activation [B][len][xc]
@@ -259,20 +240,20 @@ static int wu_network(sddm_ctx* c, const float* cond, const float* x_t, int B, i
       const bool up_pre = p.find("upsampling") != std::string::npos && p.find("pre_shortcut") != std::string::npos;
       if (stem) {
         WUInStatsArgs ia{cond, x_t, B, (int)len, wf(p + "g1"), wf(p + "e1"), 1e-5f, scale, shift, t_dev};
-        WU_LAUNCH("wu_in_stats", launch_wu_in_stats(ia, s));
+        TRY_LAUNCH("wu_in_stats", launch_wu_in_stats(ia, s));
         WUStemArgs sa{cond, x_t, scale, shift, wf(p + "w1"), wf(p + "b1"), wf(p + "nw"), wf(p + "nb"), lv, act(hn), stats, B, (int)len};
-        WU_LAUNCH("wu_stem", launch_wu_stem(dt, sa, s));
+        TRY_LAUNCH("wu_stem", launch_wu_stem(dt, sa, s));
         cur_slots = 8 * (int)((len + kWuStemTile - 1) / kWuStemTile);
       } else {
-        WU_TRY(finalize(r.ci, r.g, len, p + "g1", p + "e1"));
+        TRY(finalize(r.ci, r.g, len, p + "g1", p + "e1"));
         WUConvArgs a{};
         a.mode = WU_CONV5; a.src = x; a.Lin = (int)len; a.Cin = r.ci; a.scale = scale; a.shift = shift;
         a.w = W.base + d.woff.at(p + "w1"); a.bias = wf(p + "b1"); a.nw = wf(p + "nw"); a.nb = wf(p + "nb"); a.lv = lv;
         a.out = act(hn); a.Lout = (int)len; a.Cout = r.co; a.stats = stats; a.B = B;
-        WU_LAUNCH("wu_conv block1", launch_wu_conv(dt, a, s));
+        TRY_LAUNCH("wu_conv block1", launch_wu_conv(dt, a, s));
         cur_slots = wu_conv_slots((int)len);
       }
-      WU_TRY(finalize(r.co, r.g, len, p + "g2", p + "e2"));
+      TRY(finalize(r.co, r.g, len, p + "g2", p + "e2"));
       WUConvArgs a{};
       a.mode = WU_CONV5; a.src = act(hn); a.Lin = (int)len; a.Cin = r.co; a.scale = scale; a.shift = shift;
       a.w = W.base + d.woff.at(p + "w2"); a.bias = wf(p + "b2");
@@ -284,7 +265,7 @@ static int wu_network(sddm_ctx* c, const float* cond, const float* x_t, int B, i
         shortcuts.pop_back();
       }
       a.out = act(on); a.Lout = (int)len; a.Cout = r.co; a.stats = stats; a.B = B;
-      WU_LAUNCH("wu_conv block2", launch_wu_conv(dt, a, s));
+      TRY_LAUNCH("wu_conv block2", launch_wu_conv(dt, a, s));
       cur_slots = wu_conv_slots((int)len);
       if (p.find("downsampling") != std::string::npos && p.find("pre_shortcut") != std::string::npos) shortcuts.push_back(on);
       x = act(on);
@@ -295,61 +276,17 @@ static int wu_network(sddm_ctx* c, const float* cond, const float* x_t, int B, i
       a.mode = q.up ? WU_UP4 : WU_DOWN4; a.src = x; a.Lin = (int)len; a.Cin = q.c;
       a.w = W.base + d.woff.at(q.p + "w"); a.bias = wf(q.p + "b");
       a.out = act("r" + q.p); a.Lout = (int)lout; a.Cout = q.c; a.stats = stats; a.B = B;
-      WU_LAUNCH("wu_conv resample", launch_wu_conv(dt, a, s));
+      TRY_LAUNCH("wu_conv resample", launch_wu_conv(dt, a, s));
       cur_slots = wu_conv_slots((int)lout);
       len = lout;
-      WU_TRY(finalize(q.c, q.c / 8, len, q.p + "g", q.p + "e"));
+      TRY(finalize(q.c, q.c / 8, len, q.p + "g", q.p + "e"));
       WUActArgs aa{act("r" + q.p), scale, shift, act("y" + q.p), stats, B, (int)len, q.c};
-      WU_LAUNCH("wu_act", launch_wu_act(dt, aa, s));
+      TRY_LAUNCH("wu_act", launch_wu_act(dt, aa, s));
       cur_slots = (int)((len + kWuActTile - 1) / kWuActTile);
       x = act("y" + q.p);
     }
   }
   WUHeadArgs ha{x, wf("out.w"), wf("out.b"), d.act.at<float>(d.aoff.at("eps")), B, (int)N};
-  WU_LAUNCH("wu_head", launch_wu_head(dt, ha, s));
-  return SDDM_OK;
-}
-
-// The reverse loop of SDDM.infer (model.py:50-124) over Waveunet3: cond = waveform [B][1][N], the
-// initial state and the transition of the context's p_transition; out [B][1][N]
-static int wu_sample(sddm_ctx* c, const float* cond, int64_t B, int64_t N, uint64_t seed, int64_t row_offset, float* out,
-                     float* record, int sample_inter, const float* noise, hipStream_t s) {
-  WUState& d = *c->wus;
-  WU_TRY(wu_check_shape(B, N));
-  WU_TRY(wu_prepare(c, (int)B, N));
-  const int T = c->T;
-  InitArgs ia{};                                       // x_T (model.py:57-68)
-  ia.mode = c->init_mode; ia.cond = cond; ia.out = out; ia.total = B * N; ia.N = N; ia.T = T;
-  ia.co = c->coef(); ia.seed = seed; ia.row_offset = row_offset; ia.noise = noise;
-  SDDM_HIP_CHECK(launch_init_state(ia, s));
-  StepParams* sp = c->warena.at<StepParams>(d.off_sp);
-  SDDM_HIP_CHECK(launch_set_params(sp, T + 1, seed, row_offset, s));
-  const WULevel lv{nullptr, c->dtab(3), c->noise_time_step, &sp->t};   // sqrt_alpha_bar[t] or t (model.py:84-89)
-  int64_t nrec = 0;
-  float* eps = d.act.at<float>(d.aoff.at("eps"));
-  for (int t = T; t >= 1; --t) {
-    WU_TRY(wu_network(c, cond, out, (int)B, N, lv, &sp->t, s));
-    TransArgs ta{};                                    // p_transition* (diffusion.py:164-223)
-    ta.mode = c->tr_mode; ta.x_t = out; ta.eps = eps; ta.cond = cond; ta.out = out;
-    ta.total = B * N; ta.N = N; ta.t = t; ta.t_dev = &sp->t; ta.co = c->coef(); ta.seed = seed; ta.row_offset = row_offset;
-    ta.noise = noise; ta.noise_ld = B * N;
-    SDDM_HIP_CHECK(launch_transition(ta, s));
-    if (record && t % sample_inter == 0) {
-      SDDM_HIP_CHECK(hipMemcpyAsync(record + nrec * B * N, out, sizeof(float) * B * N, hipMemcpyDeviceToDevice, s));
-      ++nrec;
-    }
-  }
-  return SDDM_OK;
-}
-
-// one forward: cond, x_t [B][N], noise level [B] -> clamp(output_conv) [B][N]
-static int wu_forward(sddm_ctx* c, const float* cond, const float* x_t, const float* noise_level, int64_t B, int64_t N,
-                      float* eps_out, hipStream_t s) {
-  WUState& d = *c->wus;
-  WU_TRY(wu_check_shape(B, N));
-  WU_TRY(wu_prepare(c, (int)B, N));
-  const WULevel lv{noise_level, nullptr, 0, nullptr};
-  WU_TRY(wu_network(c, cond, x_t, (int)B, N, lv, nullptr, s));
-  SDDM_HIP_CHECK(hipMemcpyAsync(eps_out, d.act.at<float>(d.aoff.at("eps")), sizeof(float) * B * N, hipMemcpyDeviceToDevice, s));
+  TRY_LAUNCH("wu_head", launch_wu_head(dt, ha, s));
   return SDDM_OK;
 }

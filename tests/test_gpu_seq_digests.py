@@ -1,0 +1,151 @@
+"""The output bits of the sequential networks (DiffWave, the WaveGrad family, Waveunet3), pinned
+across changes of the host code that drives them.
+
+None of their kernels uses an atomic and every path's own tests assert run-to-run bit equality, so
+host-side work on the runtime (the sampling loop, the forward wrapper, the weight packer, the
+workspace cache) has an exact criterion: every output bit stays.  tests/golden/seq_path_digests.json
+holds SHA-256 digests of the outputs below, recorded on the GPU with the library of the commit
+before the paths were given one loop and one packer (tools/record_store_digests.py --module
+test_gpu_seq_digests); every case asserts digest equality.
+
+Cases are <net>/<dtype>/<kind>, B = 2, N = two hops (296 for Waveunet3: the smallest sizes of the
+path tests at which every level has more than one position), T = 4, one library context per
+(net, dtype).  The spectrogram nets run under their only mode, the waveform-conditioned ones under
+p_transition "conditional" (the condition enters the initial state and the transition).  DiffWave
+and Waveunet3-time_step take the step as the noise condition, the rest sqrt_alpha_bar.
+  fw       network_forward at distinct noise levels
+  sample   sample, seed 7, row_offset 3
+  record   sample_continuous, sample_inter 2: out, then the two recorded states
+  noise    sample_noise with seeded draws [T + 1][B][1][N]
+  reshape  fw, a forward at B = 3 and another length on the same context, fw again: both equal the
+           pinned fw digest (the workspace cache)
+"""
+import functools
+import hashlib
+import json
+import os
+
+import numpy as np
+import pytest
+
+import _denoise_wavegrad_oracle as DO
+import _waveunet3_oracle as WO
+from _helpers import GOLDEN, diffwave_params, wavegrad_params
+from _weights import make_params
+
+pytestmark = pytest.mark.gpu
+
+FIXTURE = os.path.join(GOLDEN, "seq_path_digests.json")
+B, T = 2, 4
+# net -> (network type, N, another N for the reshape case, spectrogram bins or 0, hop, noise_condition)
+NETS = {"DiffWave": ("DiffWave", 512, 768, 513, 256, "time_step"),
+        "WaveGrad": ("WaveGrad", 600, 900, 128, 300, "sqrt_alpha_bar"),
+        "DenoiseWaveGrad1": ("DenoiseWaveGrad1", 800, 1200, 0, 400, "sqrt_alpha_bar"),
+        "DenoiseWaveGrad3": ("DenoiseWaveGrad3", 600, 900, 0, 300, "sqrt_alpha_bar"),
+        "Waveunet3": ("Waveunet3", 296, 304, 0, 1, "sqrt_alpha_bar"),
+        "Waveunet3-time_step": ("Waveunet3", 296, 304, 0, 1, "time_step")}
+KINDS = ("fw", "sample", "record", "noise", "reshape")
+CASES = [f"{n}/{d}/{k}" for n in NETS for d in ("float32", "bfloat16") for k in KINDS]
+
+_CTX = {}
+
+
+@functools.lru_cache(maxsize=None)
+def _params(net_type):
+    if net_type == "DiffWave":
+        return diffwave_params()
+    if net_type == "WaveGrad":
+        return wavegrad_params()
+    if net_type == "Waveunet3":
+        return make_params(WO.param_shapes(), 0)
+    return make_params(DO.param_shapes(net_type), 0)
+
+
+def _ctx(net, dtype):
+    if (net, dtype) not in _CTX:
+        import sddm_hip
+        net_type, _, _, bins, hop, nc = NETS[net]
+        if bins:
+            arch = {"type": "SDDM_spectrogram", "args": {"noise_condition": nc, "hop_samples": hop}}
+        else:
+            arch = {"type": "SDDM", "args": {"noise_condition": nc, "p_transition": "conditional",
+                                             "q_transition": "original"}}
+        cfg = {"arch": arch,
+               "diffusion": {"type": "GaussianDiffusion",
+                             "args": {"schedule": "linear", "n_timestep": T, "linear_start": 1e-4, "linear_end": 0.05}},
+               "network": {"type": net_type, "args": dict(WO.ARGS) if net_type == "Waveunet3" else {}},
+               "num_samples": -1}
+        ctx = sddm_hip.Context(cfg, 0, dtype)
+        ctx.load_state_dict(_params(net_type))
+        assert ctx.missing() == 0
+        _CTX[net, dtype] = ctx
+    return _CTX[net, dtype]
+
+
+def _inputs(net, rows, N, seed):
+    """cond (spectrogram [rows][bins][F] or waveform [rows][1][N]), x_t [rows][1][N], distinct levels [rows]."""
+    _, _, _, bins, hop, _ = NETS[net]
+    rng = np.random.default_rng(seed)
+    if bins:
+        cond = rng.uniform(0, 1, (rows, bins, N // hop)).astype(np.float32)
+    else:
+        cond = np.clip(0.3 * rng.standard_normal((rows, 1, N)), -1, 1).astype(np.float32)
+    x_t = rng.standard_normal((rows, 1, N)).astype(np.float32)
+    nl = np.linspace(0.95, 0.15, rows).astype(np.float32)
+    return cond, x_t, nl
+
+
+def digest(a):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    return hashlib.sha256(a.tobytes()).hexdigest()
+
+
+def _forward(torch, ctx, net, rows, N, seed):
+    dev = torch.device("cuda", 0)
+    cond, x_t, nl = (torch.from_numpy(a).to(dev) for a in _inputs(net, rows, N, seed))
+    eps = torch.full((rows, 1, N), float("nan"), device=dev)
+    ctx.network_forward(cond, x_t, nl, eps)
+    torch.cuda.synchronize()
+    return eps.cpu().numpy()
+
+
+def run_case(torch, case):
+    """The output array of one case (fp32 on the host)."""
+    net, dtype, kind = case.split("/")
+    N, N2 = NETS[net][1:3]
+    ctx = _ctx(net, dtype)
+    dev = torch.device("cuda", 0)
+    if kind == "fw":
+        return _forward(torch, ctx, net, B, N, 5)
+    if kind == "reshape":
+        first = _forward(torch, ctx, net, B, N, 5)
+        other = _forward(torch, ctx, net, 3, N2, 6)
+        assert np.isfinite(other).all() and np.abs(other).max() > 0
+        again = _forward(torch, ctx, net, B, N, 5)
+        assert digest(first) == digest(again), "the forward changed after a forward at another shape"
+        return again
+    cond = torch.from_numpy(_inputs(net, B, N, 9)[0]).to(dev)
+    out = torch.full((B, 1, N), float("nan"), device=dev)
+    if kind == "sample":
+        ctx.sample(cond, out, 7, 3)
+    elif kind == "record":
+        record = torch.full((T // 2, B, 1, N), float("nan"), device=dev)
+        ctx.sample_continuous(cond, out, record, 2, 7, 3)
+        out = torch.cat([out[None], record])
+    else:
+        draws = np.random.default_rng(11).standard_normal((T + 1, B, 1, N)).astype(np.float32)
+        ctx.sample_noise(cond, out, torch.from_numpy(draws).to(dev))
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_output_digest_is_pinned(torch_cuda, case):
+    pinned = json.load(open(FIXTURE))["digests"]
+    out = run_case(torch_cuda, case)
+    assert np.isfinite(out).all() and np.abs(out).max() > 0
+    got = digest(out)
+    print(f"{case}: {got[:16]} (pinned {pinned[case][:16]})")
+    assert got == pinned[case]
+    if case.endswith("/reshape"):
+        assert got == pinned[case.rsplit("/", 1)[0] + "/fw"]

@@ -1,12 +1,15 @@
-"""Record tests/golden/unet_store_digests.json: SHA-256 of the outputs of every case of
-tests/test_gpu_store_flavour.py, computed on the GPU with the library that SDDM_LIB names (build the
-commit to pin as a variant: SDDM_BUILD_VARIANT=parent python .../sddm_hip/build.py).
+"""Record the digest fixture of a test module (its FIXTURE): SHA-256 of the outputs of every one of
+its CASES, computed on the GPU with the library that SDDM_LIB names (build the commit to pin as a
+variant: SDDM_BUILD_VARIANT=parent python .../sddm_hip/build.py).
 
-    SDDM_LIB=tools/_parent/libsddm_hip.so python tools/record_store_digests.py [--out FILE] [--check]
+    SDDM_LIB=tools/_parent/libsddm_hip.so python tools/record_store_digests.py [--module NAME] [--out FILE] [--check]
 
+--module: test_gpu_store_flavour (tests/golden/unet_store_digests.json, the default) or
+test_gpu_seq_digests (tests/golden/seq_path_digests.json).
 --check compares against the committed fixture instead of writing (any library).
 """
 import argparse
+import importlib
 import json
 import os
 import sys
@@ -19,13 +22,14 @@ for p in (REPO, os.path.join(REPO, "speech-denoising-diffusion-model-2_amd"), os
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--module", default="test_gpu_store_flavour")
     ap.add_argument("--out", default=None)
     ap.add_argument("--check", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import torch
     import sddm_hip
-    import test_gpu_store_flavour as sf
+    sf = importlib.import_module(a.module)
     pinned = json.load(open(sf.FIXTURE))["digests"] if a.check else {}
     digests, bad = {}, []
     for case in sf.CASES:
@@ -38,7 +42,7 @@ def main():
             print(f"{case}: REFUSED {e}", flush=True)             # the plan or a launcher refused the table
             bad.append(case)
             continue
-        assert np.isfinite(out).all(), case
+        assert np.isfinite(out).all() and np.abs(out).max() > 0, case
         digests[case] = sf.digest(out)
         note = ""
         if a.check and digests[case] != pinned.get(case):
