@@ -10,32 +10,17 @@ namespace sddm {
 // [B][C] that launch_wu_gn_finalize (wu_kernels.h) makes of the producer's statistics partials
 // [B][nslots][C][2].  The noise level of a row is a WULevel, as for Waveunet3.
 
-// ---- stem: raw = Conv1d(2, 24, 5, padding 2) of cat(cond, y_t) (no norm on the raw input), with the
-// statistics partials of what it stored.  Decrements the device step counter (the first launch of a
-// reverse step; nothing in this kernel reads the counter)
-constexpr int kWu2StemTile = 256;         // positions per block; 8 statistics slots per block
+// ---- stem: raw = Conv1d(2, 24, 5, padding 2) of cat(cond, y_t) (no norm on the raw input): WUStemArgs
+// (wu_kernels.h) with w [24][2][5], bias [24] and t_dev
 constexpr int kWu2StemC = 24;
-struct WU2StemArgs {
-  const float* cond; const float* x;      // [B][L] fp32
-  const float* w; const float* bias;      // [24][2][5], [24] fp32
-  void* out; float* stats; int B, L;      // [B][L][24] (T), [B][8 ceil(L / 256)][24][2]
-  int* t_dev;                             // or null (a forward)
-};
-hipError_t launch_wu2_stem(int dtype, const WU2StemArgs& a, hipStream_t s);
+hipError_t launch_wu2_stem(int dtype, const WUStemArgs& a, hipStream_t s);
 
-// ---- the MFMA implicit-GEMM convolution for channel counts that are multiples of 8
-//   WU2_CONV5: 5 taps, stride 1, padding 2               (ConvLayer convs)
-//   WU2_CONV3: 3 taps, stride 1, padding 1               (FiLM input_conv / output_conv)
-//   WU2_DOWN4: 4 taps, stride 2, padding 1, Lout = Lin/2 (DownsampleLayer)
-//   WU2_UP4:   ConvTranspose1d 4 taps, stride 2, padding 1, Lout = 2 Lin, as two output phases of
-//              2 taps each (UpsampleLayer)
+// ---- the MFMA implicit-GEMM convolution (modes: wu_kernels.h) for channel counts that are multiples of 8
 // prologue: none (scale null), or ReLU(v * scale[b][c] + shift[b][c]), then with `film`
 //   film[b][l][Cin + c] * v + film[b][l][c] (film = the FiLM output_conv's [B][Lin][2 Cin]: shift
 //   first, scale second); the halo is zero after all of it.
 // epilogue: + bias, then with enc_dim > 0 leaky_relu(0.2) + PositionalEncoding(level)[c]
 //   (enc_dim == Cout), store, statistics partials (stats null: none).
-enum { WU2_CONV5 = 0, WU2_CONV3 = 1, WU2_DOWN4 = 2, WU2_UP4 = 3 };
-constexpr int kWu2Tile = 128;             // output positions per block; 4 statistics slots per block
 struct WU2ConvArgs {
   int mode;
   const void* src; int Lin, Cin;          // [B][Lin][Cin] (T), Cin % 8 == 0, <= 96
@@ -48,7 +33,6 @@ struct WU2ConvArgs {
   int B;
 };
 hipError_t launch_wu2_conv(int dtype, const WU2ConvArgs& a, hipStream_t s);
-inline int wu2_conv_slots(int Lout) { return 4 * ((Lout + kWu2Tile - 1) / kWu2Tile); }   // statistics slots of a launch
 
 // ---- head: eps = clamp(Conv1x1 24 -> 1 of ReLU(GN(raw)), -1, 1) as fp32 [B][L]
 struct WU2HeadArgs {

@@ -28,6 +28,7 @@
 // 1 + 18 + 19 + 6 + 1 + 1 = 46.
 #pragma once
 #include "wu2_kernels.h"
+#include "wu_host.h"
 
 namespace wu2 {
 constexpr int kC[4] = {24, 48, 72, 96};
@@ -38,21 +39,21 @@ static std::vector<Layer> build_net() {
   std::vector<Layer> n;
   for (int i = 0; i < 3; ++i) {
     const std::string p = "waveunet.downsampling_blocks." + std::to_string(i) + ".";
-    n.push_back({p + "pre_shortcut_convs.0.", sddm::WU2_CONV5, i == 0 ? 2 : kC[i], kC[i], i, -1});
-    n.push_back({p + "post_shortcut_convs.0.", sddm::WU2_CONV5, kC[i], kC[i + 1], -1, -1});
-    n.push_back({p + "downconv.down.", sddm::WU2_DOWN4, kC[i + 1], kC[i + 1], -1, -1});
+    n.push_back({p + "pre_shortcut_convs.0.", sddm::WU_CONV5, i == 0 ? 2 : kC[i], kC[i], i, -1});
+    n.push_back({p + "post_shortcut_convs.0.", sddm::WU_CONV5, kC[i], kC[i + 1], -1, -1});
+    n.push_back({p + "downconv.down.", sddm::WU_DOWN4, kC[i + 1], kC[i + 1], -1, -1});
   }
-  n.push_back({"waveunet.bottlenecks.0.", sddm::WU2_CONV5, kC[3], kC[3], -1, -1});
+  n.push_back({"waveunet.bottlenecks.0.", sddm::WU_CONV5, kC[3], kC[3], -1, -1});
   for (int j = 0; j < 3; ++j) {
     const int i = 3 - j;
     const std::string p = "waveunet.upsampling_blocks." + std::to_string(j) + ".";
-    n.push_back({p + "upconv.up.", sddm::WU2_UP4, kC[i], kC[i], -1, -1});
-    n.push_back({p + "pre_shortcut_convs.0.", sddm::WU2_CONV5, kC[i], kC[i - 1], -1, -1});
-    n.push_back({p + "post_shortcut_convs.0.", sddm::WU2_CONV5, kC[i - 1], kC[i - 1], -1, i - 1});
+    n.push_back({p + "upconv.up.", sddm::WU_UP4, kC[i], kC[i], -1, -1});
+    n.push_back({p + "pre_shortcut_convs.0.", sddm::WU_CONV5, kC[i], kC[i - 1], -1, -1});
+    n.push_back({p + "post_shortcut_convs.0.", sddm::WU_CONV5, kC[i - 1], kC[i - 1], -1, i - 1});
   }
   return n;
 }
-inline int taps(int mode) { return mode == sddm::WU2_CONV5 ? 5 : (mode == sddm::WU2_CONV3 ? 3 : 4); }
+inline int taps(int mode) { return mode == sddm::WU_CONV5 ? 5 : (mode == sddm::WU_CONV3 ? 3 : 4); }
 inline std::string film(int i) { return "waveunet.film_blocks." + std::to_string(i) + "."; }
 }  // namespace wu2
 
@@ -88,7 +89,7 @@ static std::map<std::string, std::vector<int64_t>> wu2_param_shapes(const std::v
   std::map<std::string, std::vector<int64_t>> s;
   for (const wu2::Layer& l : n) {
     const int k = wu2::taps(l.mode);
-    if (l.mode == sddm::WU2_UP4) s[l.p + "filter.weight"] = {l.ci, l.co, k};   // ConvTranspose1d: [ci][co][k]
+    if (l.mode == sddm::WU_UP4) s[l.p + "filter.weight"] = {l.ci, l.co, k};   // ConvTranspose1d: [ci][co][k]
     else s[l.p + "filter.weight"] = {l.co, l.ci, k};
     s[l.p + "filter.bias"] = {l.co};
     s[l.p + "norm.weight"] = {l.co}; s[l.p + "norm.bias"] = {l.co};
@@ -104,31 +105,19 @@ static std::map<std::string, std::vector<int64_t>> wu2_param_shapes(const std::v
 }
 
 size_t WU2State::pack(sddm_ctx* c, WeightPacker& pk) {
-  const int dt = c->dtype;
-  const size_t es = dtype_size(dt);
   auto P = [&](const std::string& k) -> const std::vector<float>& { return c->params.at(k).data; };
-  // conv weight -> [co][k][ci] in the compute dtype
-  auto add_conv = [&](const std::string& name, int co, int ci, int k, const std::vector<float>& w, bool transposed) {
-    char* b = pk.raw(name, (size_t)co * k * ci * es);
-    for (int o = 0; o < co; ++o)
-      for (int i = 0; i < ci; ++i)
-        for (int t = 0; t < k; ++t) {
-          const size_t src = transposed ? ((size_t)i * co + o) * k + t : ((size_t)o * ci + i) * k + t;   // ConvTranspose1d: [ci][co][k]
-          store_elem(b, ((size_t)o * k + t) * ci + i, w[src], dt);
-        }
-  };
   for (const wu2::Layer& l : net) {
     if (l.ci == 2) pk.f32(l.p + "w", P(l.p + "filter.weight"));                  // stem: fp32 [24][2][5], VALU kernel
-    else add_conv(l.p + "w", l.co, l.ci, wu2::taps(l.mode), P(l.p + "filter.weight"), l.mode == sddm::WU2_UP4);
+    else wu_add_conv(c, pk, l.p + "w", l.co, l.ci, wu2::taps(l.mode), P(l.p + "filter.weight"), l.mode == sddm::WU_UP4);
     pk.f32(l.p + "b", P(l.p + "filter.bias"));
     pk.f32(l.p + "g", P(l.p + "norm.weight"));
     pk.f32(l.p + "e", P(l.p + "norm.bias"));
   }
   for (int i = 0; i < 3; ++i) {
     const std::string f = wu2::film(i);
-    add_conv(f + "iw", wu2::kC[i], wu2::kC[i], 3, P(f + "input_conv.weight"), false);
+    wu_add_conv(c, pk, f + "iw", wu2::kC[i], wu2::kC[i], 3, P(f + "input_conv.weight"), false);
     pk.f32(f + "ib", P(f + "input_conv.bias"));
-    add_conv(f + "ow", 2 * wu2::kC[i], wu2::kC[i], 3, P(f + "output_conv.weight"), false);
+    wu_add_conv(c, pk, f + "ow", 2 * wu2::kC[i], wu2::kC[i], 3, P(f + "output_conv.weight"), false);
     pk.f32(f + "ob", P(f + "output_conv.bias"));
   }
   pk.f32("out.w", P("waveunet.output_conv.weight"));
@@ -139,9 +128,7 @@ size_t WU2State::pack(sddm_ctx* c, WeightPacker& pk) {
 // activation buffers for (B, N): name -> [B][len][C] in the compute dtype
 int WU2State::prepare(sddm_ctx* c, int64_t B, int64_t N) {
   WU2State& d = *this;
-  if (B < 1 || B > 65535) FAIL(SDDM_ERR_INVALID_ARG, "batch %lld", (long long)B);
-  if (N < 8 || N % 8) FAIL(SDDM_ERR_SHAPE, "%lld samples is not a positive multiple of 8 (Waveunet2 halves the length three times)", (long long)N);
-  if (N > (int64_t)1 << 30) FAIL(SDDM_ERR_SHAPE, "%lld samples: Waveunet2 positions are 32-bit", (long long)N);
+  TRY(wu_check_shape("Waveunet2", B, N));
   if (d.B == B && d.N == N) return SDDM_OK;
   const size_t es = dtype_size(c->dtype);
   Arena& A = d.act;
@@ -151,8 +138,8 @@ int WU2State::prepare(sddm_ctx* c, int64_t B, int64_t N) {
   int64_t len = N;
   for (size_t k = 0; k < d.net.size(); ++k) {
     const wu2::Layer& l = d.net[k];
-    if (l.mode == sddm::WU2_DOWN4) len /= 2;
-    if (l.mode == sddm::WU2_UP4) len *= 2;
+    if (l.mode == sddm::WU_DOWN4) len /= 2;
+    if (l.mode == sddm::WU_UP4) len *= 2;
     buf("r" + std::to_string(k), len, l.co);           // the layer's raw conv output
     if (l.film >= 0) {
       buf("fi" + std::to_string(l.film), len, l.co);   // FiLM input_conv's output
@@ -160,7 +147,7 @@ int WU2State::prepare(sddm_ctx* c, int64_t B, int64_t N) {
     }
   }
   // statistics partials of the latest producer: stem 8 slots per 256 positions, convs 4 per 128
-  const int64_t max_slots = 8 * ((N + kWu2StemTile - 1) / kWu2StemTile) + 8;
+  const int64_t max_slots = 8 * ((N + kWuStemTile - 1) / kWuStemTile) + 8;
   d.aoff["stats"] = A.reserve(sizeof(float) * (size_t)B * max_slots * 96 * 2);
   d.aoff["scale"] = A.reserve(sizeof(float) * (size_t)B * 96);
   d.aoff["shift"] = A.reserve(sizeof(float) * (size_t)B * 96);
@@ -174,8 +161,7 @@ int WU2State::prepare(sddm_ctx* c, int64_t B, int64_t N) {
 // the noise level the FiLM encodings take: sqrt_alpha_bar[t] or t of the step counter (sampling,
 // model.py:84-89) or the caller's [B] (a forward).  No launch
 int WU2State::begin(sddm_ctx* c, const float*, const float* noise_level, hipStream_t) {
-  if (noise_level) lv = WULevel{noise_level, nullptr, 0, nullptr};
-  else lv = WULevel{nullptr, c->dtab(3), c->noise_time_step, &c->warena.at<StepParams>(off_sp)->t};
+  lv = wu_begin_level(c, noise_level, off_sp);
   return SDDM_OK;
 }
 
@@ -194,13 +180,15 @@ int WU2State::network(sddm_ctx* c, const float* cond, const float* x_t, int, int
   int64_t len = d.N;
   for (size_t k = 0; k < d.net.size(); ++k) {
     const wu2::Layer& l = d.net[k];
-    const int64_t lout = l.mode == sddm::WU2_DOWN4 ? len / 2 : (l.mode == sddm::WU2_UP4 ? len * 2 : len);
+    const int64_t lout = l.mode == sddm::WU_DOWN4 ? len / 2 : (l.mode == sddm::WU_UP4 ? len * 2 : len);
     char* out = act("r" + std::to_string(k));
     int slots;
     if (l.ci == 2) {
-      WU2StemArgs sa{cond, x_t, wf(l.p + "w"), wf(l.p + "b"), out, stats, B, (int)len, t_dev};
+      WUStemArgs sa{};
+      sa.cond = cond; sa.x = x_t; sa.w = wf(l.p + "w"); sa.bias = wf(l.p + "b");
+      sa.out = out; sa.stats = stats; sa.B = B; sa.L = (int)len; sa.t_dev = t_dev;
       TRY_LAUNCH("wu2_stem", launch_wu2_stem(dt, sa, s));
-      slots = 8 * (int)((len + kWu2StemTile - 1) / kWu2StemTile);
+      slots = 8 * (int)((len + kWuStemTile - 1) / kWuStemTile);
     } else {
       WU2ConvArgs a{};
       a.mode = l.mode; a.src = x; a.Lin = (int)len; a.Cin = l.ci; a.scale = scale; a.shift = shift;
@@ -208,7 +196,7 @@ int WU2State::network(sddm_ctx* c, const float* cond, const float* x_t, int, int
       a.w = W.base + d.woff.at(l.p + "w"); a.bias = wf(l.p + "b");
       a.out = out; a.Lout = (int)lout; a.Cout = l.co; a.stats = stats; a.B = B;
       TRY_LAUNCH("wu2_conv ConvLayer", launch_wu2_conv(dt, a, s));
-      slots = wu2_conv_slots((int)lout);
+      slots = wu_conv_slots((int)lout);
     }
     len = lout;
     x = out;
@@ -217,12 +205,12 @@ int WU2State::network(sddm_ctx* c, const float* cond, const float* x_t, int, int
     if (l.film >= 0) {                                 // FiLM of the shortcut (waveunet2.py:56-61)
       const std::string f = wu2::film(l.film), n = std::to_string(l.film);
       WU2ConvArgs a{};
-      a.mode = WU2_CONV3; a.src = x; a.Lin = (int)len; a.Cin = l.co; a.scale = scale; a.shift = shift;
+      a.mode = WU_CONV3; a.src = x; a.Lin = (int)len; a.Cin = l.co; a.scale = scale; a.shift = shift;
       a.w = W.base + d.woff.at(f + "iw"); a.bias = wf(f + "ib"); a.enc_dim = l.co; a.lv = lv;
       a.out = act("fi" + n); a.Lout = (int)len; a.Cout = l.co; a.B = B;
       TRY_LAUNCH("wu2_conv FiLM input_conv", launch_wu2_conv(dt, a, s));
       WU2ConvArgs o{};
-      o.mode = WU2_CONV3; o.src = act("fi" + n); o.Lin = (int)len; o.Cin = l.co;
+      o.mode = WU_CONV3; o.src = act("fi" + n); o.Lin = (int)len; o.Cin = l.co;
       o.w = W.base + d.woff.at(f + "ow"); o.bias = wf(f + "ob");
       o.out = act("fo" + n); o.Lout = (int)len; o.Cout = 2 * l.co; o.B = B;
       TRY_LAUNCH("wu2_conv FiLM output_conv", launch_wu2_conv(dt, o, s));

@@ -31,19 +31,27 @@ struct WUInStatsArgs {
 };
 hipError_t launch_wu_in_stats(const WUInStatsArgs& a, hipStream_t s);
 
-// ---- stem: h = Conv5(SiLU(GN(cat(cond, y_t)))) + bias + noise constant, 2 -> 32 channels (VALU)
+// ---- stem: Conv1d(2, C, 5, padding 2) of cat(cond, y_t) + bias, 2 -> C channels (VALU), with the
+// statistics partials of what it stored.  One argument struct for both networks:
+//   Waveunet3 (launch_wu_stem, C = 32): the sources go through SiLU(GN(2, 2)) from scale / shift, and
+//     the block's noise constant nw * level + nb is added; t_dev is not used (wu_in_stats steps it)
+//   Waveunet2 (launch_wu2_stem, wu2_kernels.h, C = 24): the raw sources; scale, shift, nw, nb and lv
+//     are not used.  Decrements the device step counter t_dev (the first launch of a reverse step;
+//     null in a forward)
 constexpr int kWuStemTile = 256;          // positions per block; 8 statistics slots per block
 struct WUStemArgs {
   const float* cond; const float* x; const float* scale; const float* shift;   // [B][L], [B][2]
-  const float* w; const float* bias;      // [32][2][5], [32] fp32
-  const float* nw; const float* nb;       // Linear(1, 32) of the block's noise_func
+  const float* w; const float* bias;      // [C][2][5], [C] fp32
+  const float* nw; const float* nb;       // Waveunet3: Linear(1, C) of the block's noise_func
   WULevel lv;
-  void* out; float* stats; int B, L;      // [B][L][32] (T), [B][8 ceil(L / 256)][32][2]
+  void* out; float* stats; int B, L;      // [B][L][C] (T), [B][8 ceil(L / 256)][C][2]
+  int* t_dev;
 };
 hipError_t launch_wu_stem(int dtype, const WUStemArgs& a, hipStream_t s);
 
-// ---- the MFMA implicit-GEMM convolution
-//   WU_CONV5: 5 taps, stride 1, padding 2               (Block convs)
+// ---- the MFMA implicit-GEMM convolution (one kernel for both networks, wu_conv_impl.h)
+//   WU_CONV5: 5 taps, stride 1, padding 2               (Block / ConvLayer convs)
+//   WU_CONV3: 3 taps, stride 1, padding 1               (Waveunet2 only: FiLM input_conv / output_conv)
 //   WU_DOWN4: 4 taps, stride 2, padding 1, Lout = Lin/2 (DownsampleLayer)
 //   WU_UP4:   ConvTranspose1d 4 taps, stride 2, padding 1, Lout = 2 Lin, as two output phases of
 //             2 taps each (UpsampleLayer)
@@ -52,7 +60,8 @@ hipError_t launch_wu_stem(int dtype, const WUStemArgs& a, hipStream_t s);
 // residual: 1 identity (res [B][Lout][Cout]), 2 the 1x1 res_conv as extra K steps over the block's
 //   un-normalised input (res [B][Lout][RC], rw [Cout][RC]; its bias is folded into `bias`), 3 the
 //   first block's 2 -> 32 res_conv on the raw fp32 inputs (rw2 [Cout][2], bias folded likewise)
-enum { WU_CONV5 = 0, WU_DOWN4 = 1, WU_UP4 = 2 };
+// The above is Waveunet3's launch (no WU_CONV3); Waveunet2's is in wu2_kernels.h.
+enum { WU_CONV5 = 0, WU_CONV3 = 1, WU_DOWN4 = 2, WU_UP4 = 3 };
 constexpr int kWuTile = 128;              // output positions per block; 4 statistics slots per block
 struct WUConvArgs {
   int mode;

@@ -26,7 +26,7 @@
 // 27 MFMA Block convs (13 block1 + 14 block2) with one finalize each, 6 ConvLayers of three (conv,
 // finalize, wu_act), head 1, transition 1 -- 1 + 1 + 27 + 27 + 18 + 1 + 1 = 76.
 #pragma once
-#include "wu_kernels.h"
+#include "wu_host.h"
 
 namespace wu {
 constexpr int kC[4] = {32, 64, 96, 128};
@@ -114,20 +114,8 @@ static std::map<std::string, std::vector<int64_t>> wu_param_shapes(const wu::Net
 
 size_t WUState::pack(sddm_ctx* c, WeightPacker& pk) {
   const WUState& d = *this;
-  const int dt = c->dtype;
-  const size_t es = dtype_size(dt);
   auto P = [&](const std::string& k) -> const std::vector<float>& { return c->params.at(k).data; };
   auto add_f32 = [&](const std::string& name, const std::vector<float>& v) { pk.f32(name, v); };
-  // conv weight -> [co][k][ci] in the compute dtype; src index of (o, i, t) given by the caller
-  auto add_conv = [&](const std::string& name, int co, int ci, int k, const std::vector<float>& w, bool transposed) {
-    char* b = pk.raw(name, (size_t)co * k * ci * es);
-    for (int o = 0; o < co; ++o)
-      for (int i = 0; i < ci; ++i)
-        for (int t = 0; t < k; ++t) {
-          const size_t src = transposed ? ((size_t)i * co + o) * k + t : ((size_t)o * ci + i) * k + t;   // ConvTranspose1d: [ci][co][k]
-          store_elem(b, ((size_t)o * k + t) * ci + i, w[src], dt);
-        }
-  };
   for (const wu::Res& r : d.net.res) {
     const std::string& p = r.p;
     add_f32(p + "nw", P(p + "noise_func.noise_func.0.weight"));
@@ -136,21 +124,21 @@ size_t WUState::pack(sddm_ctx* c, WeightPacker& pk) {
     add_f32(p + "e1", P(p + "block1.block.0.bias"));
     add_f32(p + "b1", P(p + "block1.block.3.bias"));
     if (r.ci == 2) add_f32(p + "w1", P(p + "block1.block.3.weight"));           // stem: fp32 [32][2][5], VALU kernel
-    else add_conv(p + "w1", r.co, r.ci, 5, P(p + "block1.block.3.weight"), false);
+    else wu_add_conv(c, pk, p + "w1", r.co, r.ci, 5, P(p + "block1.block.3.weight"), false);
     add_f32(p + "g2", P(p + "block2.block.0.weight"));
     add_f32(p + "e2", P(p + "block2.block.0.bias"));
-    add_conv(p + "w2", r.co, r.co, 5, P(p + "block2.block.3.weight"), false);
+    wu_add_conv(c, pk, p + "w2", r.co, r.co, 5, P(p + "block2.block.3.weight"), false);
     std::vector<float> b2 = P(p + "block2.block.3.bias");
     if (r.ci != r.co) {                                                         // res_conv's bias rides on block2's
       const std::vector<float>& rb = P(p + "res_conv.bias");
       for (int i = 0; i < r.co; ++i) b2[i] += rb[i];
       if (r.ci == 2) add_f32(p + "rw", P(p + "res_conv.weight"));               // fp32 [32][2]
-      else add_conv(p + "rw", r.co, r.ci, 1, P(p + "res_conv.weight"), false);
+      else wu_add_conv(c, pk, p + "rw", r.co, r.ci, 1, P(p + "res_conv.weight"), false);
     }
     add_f32(p + "b2", b2);
   }
   for (const wu::Samp& q : d.net.samp) {
-    add_conv(q.p + "w", q.c, q.c, 4, P(q.p + "filter.weight"), q.up);
+    wu_add_conv(c, pk, q.p + "w", q.c, q.c, 4, P(q.p + "filter.weight"), q.up);
     add_f32(q.p + "b", P(q.p + "filter.bias"));
     add_f32(q.p + "g", P(q.p + "norm.weight"));
     add_f32(q.p + "e", P(q.p + "norm.bias"));
@@ -163,9 +151,7 @@ size_t WUState::pack(sddm_ctx* c, WeightPacker& pk) {
 // activation buffers for (B, N): name -> [B][len][C] in the compute dtype
 int WUState::prepare(sddm_ctx* c, int64_t B, int64_t N) {
   WUState& d = *this;
-  if (B < 1 || B > 65535) FAIL(SDDM_ERR_INVALID_ARG, "batch %lld", (long long)B);
-  if (N < 8 || N % 8) FAIL(SDDM_ERR_SHAPE, "%lld samples is not a positive multiple of 8 (Waveunet3 halves the length three times)", (long long)N);
-  if (N > (int64_t)1 << 30) FAIL(SDDM_ERR_SHAPE, "%lld samples: Waveunet3 positions are 32-bit", (long long)N);
+  TRY(wu_check_shape("Waveunet3", B, N));
   if (d.B == B && d.N == N) return SDDM_OK;
   const size_t es = dtype_size(c->dtype);
   Arena& A = d.act;
@@ -202,8 +188,7 @@ int WUState::prepare(sddm_ctx* c, int64_t B, int64_t N) {
 // the noise level the ResnetBlocks add: sqrt_alpha_bar[t] or t of the step counter (sampling,
 // model.py:84-89) or the caller's [B] (a forward).  No launch
 int WUState::begin(sddm_ctx* c, const float*, const float* noise_level, hipStream_t) {
-  if (noise_level) lv = WULevel{noise_level, nullptr, 0, nullptr};
-  else lv = WULevel{nullptr, c->dtab(3), c->noise_time_step, &c->warena.at<StepParams>(off_sp)->t};
+  lv = wu_begin_level(c, noise_level, off_sp);
   return SDDM_OK;
 }
 
@@ -241,7 +226,7 @@ int WUState::network(sddm_ctx* c, const float* cond, const float* x_t, int, int*
       if (stem) {
         WUInStatsArgs ia{cond, x_t, B, (int)len, wf(p + "g1"), wf(p + "e1"), 1e-5f, scale, shift, t_dev};
         TRY_LAUNCH("wu_in_stats", launch_wu_in_stats(ia, s));
-        WUStemArgs sa{cond, x_t, scale, shift, wf(p + "w1"), wf(p + "b1"), wf(p + "nw"), wf(p + "nb"), lv, act(hn), stats, B, (int)len};
+        WUStemArgs sa{cond, x_t, scale, shift, wf(p + "w1"), wf(p + "b1"), wf(p + "nw"), wf(p + "nb"), lv, act(hn), stats, B, (int)len, nullptr};
         TRY_LAUNCH("wu_stem", launch_wu_stem(dt, sa, s));
         cur_slots = 8 * (int)((len + kWuStemTile - 1) / kWuStemTile);
       } else {

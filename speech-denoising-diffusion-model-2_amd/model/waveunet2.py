@@ -2,7 +2,8 @@
 
 The module tree only holds the parameters under the reference's state-dict keys
 (``waveunet.downsampling_blocks.0.pre_shortcut_convs.0.filter.weight`` ...); the forward runs in
-libsddm_hip (csrc/waveunet2.hip, wu2_runtime.h).  Supported: the arguments of config_waveunet2.json
+libsddm_hip (csrc/waveunet2.hip, the conv and stem kernels it shares with Waveunet3 in
+csrc/wu_conv_impl.h, wu2_runtime.h).  Supported: the arguments of config_waveunet2.json
 -- channels [24, 48, 72, 96], 5-tap convs, 4-tap stride-2 resampling, conv_type 'gn', depth 1, two
 inputs; everything else is refused by the library when the context is configured.  The chunk length
 is any positive multiple of 8 (three stride-2 levels).  The output is always clamped to [-1, 1]:

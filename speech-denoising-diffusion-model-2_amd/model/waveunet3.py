@@ -2,7 +2,8 @@
 
 The module tree only holds the parameters under the reference's state-dict keys
 (``waveunet.downsampling_blocks.0.pre_shortcut.0.res_block.block1.block.3.weight`` ...); the forward
-runs in libsddm_hip (csrc/waveunet.hip, wu_runtime.h).  Supported: the arguments of
+runs in libsddm_hip (csrc/waveunet.hip, the conv and stem kernels it shares with Waveunet2 in
+csrc/wu_conv_impl.h, wu_runtime.h).  Supported: the arguments of
 config_waveunet3.json -- channels [32, 64, 96, 128], 5-tap convs, 4-tap stride-2 resampling,
 conv_type 'gn', no attention, no noise-level embedding.  The chunk length is any positive multiple
 of 8 (three stride-2 levels).

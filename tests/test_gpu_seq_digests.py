@@ -1,24 +1,36 @@
-"""The output bits of the sequential networks (DiffWave, the WaveGrad family, Waveunet3), pinned
-across changes of the host code that drives them.
+"""The output bits of the sequential networks (DiffWave, the WaveGrad family, Waveunet3, Waveunet2),
+pinned across changes of the host code that drives them and across kernel refactors that claim bit
+equality.
 
 None of their kernels uses an atomic and every path's own tests assert run-to-run bit equality, so
 host-side work on the runtime (the sampling loop, the forward wrapper, the weight packer, the
-workspace cache) has an exact criterion: every output bit stays.  tests/golden/seq_path_digests.json
-holds SHA-256 digests of the outputs below, recorded on the GPU with the library of the commit
-before the paths were given one loop and one packer (tools/record_store_digests.py --module
-test_gpu_seq_digests); every case asserts digest equality.
+workspace cache) and a kernel refactor that keeps every float expression and every summation order
+have an exact criterion: every output bit stays.  tests/golden/seq_path_digests.json holds SHA-256
+digests of the outputs below.  Every case asserts digest equality.
 
-Cases are <net>/<dtype>/<kind>, B = 2, N = two hops (296 for Waveunet3: the smallest sizes of the
-path tests at which every level has more than one position), T = 4, one library context per
+The digests are recorded on the GPU with the library of the commit before the change they guard,
+never with the code under test (tools/record_store_digests.py --module test_gpu_seq_digests).  The
+first 60 were recorded before the paths were given one loop and one packer.  The Waveunet2,
+float16, tiles and bottom entries were recorded before the two Wave-U-Nets were given one conv
+kernel and one stem kernel; that recording reproduced the first 60.
+
+Cases are <net>/<dtype>/<kind>, B = 2, N = two hops (296 for the Waveunets: the smallest sizes of
+the path tests at which every level has more than one position), T = 4, one library context per
 (net, dtype).  The spectrogram nets run under their only mode, the waveform-conditioned ones under
 p_transition "conditional" (the condition enters the initial state and the transition).  DiffWave
-and Waveunet3-time_step take the step as the noise condition, the rest sqrt_alpha_bar.
+and the -time_step entries take the step as the noise condition, the rest sqrt_alpha_bar.
   fw       network_forward at distinct noise levels
   sample   sample, seed 7, row_offset 3
   record   sample_continuous, sample_inter 2: out, then the two recorded states
   noise    sample_noise with seeded draws [T + 1][B][1][N]
   reshape  fw, a forward at B = 3 and another length on the same context, fw again: both equal the
            pinned fw digest (the workspace cache)
+The four Waveunet entries also run fw and sample in float16 (their <f16_t> kernels), and two
+forward-only kinds in all three dtypes, the shapes of their test_forward_matches_oracle:
+  tiles    network_forward at B = 2, N = 2072 (2072 / 1036 / 518 / 259): every level has several
+           128-position tiles and a partial last one, WU_UP4 blocks use both 64-position halves
+  bottom   network_forward at B = 3, N = 8: the bottleneck is one position, the transposed conv
+           starts from one position, every tile is partial
 """
 import functools
 import hashlib
@@ -29,6 +41,7 @@ import numpy as np
 import pytest
 
 import _denoise_wavegrad_oracle as DO
+import _waveunet2_oracle as W2O
 import _waveunet3_oracle as WO
 from _helpers import GOLDEN, diffwave_params, wavegrad_params
 from _weights import make_params
@@ -46,6 +59,15 @@ NETS = {"DiffWave": ("DiffWave", 512, 768, 513, 256, "time_step"),
         "Waveunet3-time_step": ("Waveunet3", 296, 304, 0, 1, "time_step")}
 KINDS = ("fw", "sample", "record", "noise", "reshape")
 CASES = [f"{n}/{d}/{k}" for n in NETS for d in ("float32", "bfloat16") for k in KINDS]
+NETS.update({"Waveunet2": ("Waveunet2", 296, 304, 0, 1, "sqrt_alpha_bar"),
+             "Waveunet2-time_step": ("Waveunet2", 296, 304, 0, 1, "time_step")})
+WAVEUNETS = ("Waveunet3", "Waveunet3-time_step", "Waveunet2", "Waveunet2-time_step")
+NET_ARGS = {"Waveunet3": WO.ARGS, "Waveunet2": W2O.ARGS}
+SHAPES = {"tiles": (2, 2072, 12), "bottom": (3, 8, 13)}   # kind -> rows, N, seed of the inputs
+# appended behind the first 60, whose names and order stay
+CASES += [f"{n}/{d}/{k}" for n in WAVEUNETS[2:] for d in ("float32", "bfloat16") for k in KINDS]
+CASES += [f"{n}/float16/{k}" for n in WAVEUNETS for k in ("fw", "sample")]
+CASES += [f"{n}/{d}/{k}" for n in WAVEUNETS for d in ("float32", "bfloat16", "float16") for k in SHAPES]
 
 _CTX = {}
 
@@ -58,6 +80,8 @@ def _params(net_type):
         return wavegrad_params()
     if net_type == "Waveunet3":
         return make_params(WO.param_shapes(), 0)
+    if net_type == "Waveunet2":
+        return make_params(W2O.param_shapes(), 0)
     return make_params(DO.param_shapes(net_type), 0)
 
 
@@ -73,7 +97,7 @@ def _ctx(net, dtype):
         cfg = {"arch": arch,
                "diffusion": {"type": "GaussianDiffusion",
                              "args": {"schedule": "linear", "n_timestep": T, "linear_start": 1e-4, "linear_end": 0.05}},
-               "network": {"type": net_type, "args": dict(WO.ARGS) if net_type == "Waveunet3" else {}},
+               "network": {"type": net_type, "args": dict(NET_ARGS.get(net_type, {}))},
                "num_samples": -1}
         ctx = sddm_hip.Context(cfg, 0, dtype)
         ctx.load_state_dict(_params(net_type))
@@ -117,6 +141,8 @@ def run_case(torch, case):
     dev = torch.device("cuda", 0)
     if kind == "fw":
         return _forward(torch, ctx, net, B, N, 5)
+    if kind in SHAPES:
+        return _forward(torch, ctx, net, *SHAPES[kind])
     if kind == "reshape":
         first = _forward(torch, ctx, net, B, N, 5)
         other = _forward(torch, ctx, net, 3, N2, 6)
