@@ -60,8 +60,8 @@ void sddm_destroy(sddm_ctx* ctx);
  * parse_config.py:82-95).  `json` is {"arch": {...}, "diffusion": {...}, "network": {...},
  * "num_samples": N} with the reference's type names and args verbatim
  * (config_unet.json, config_diffwave.json, config_wavegrad.json, and the default config.json).
- * Network types: UNetModified2, DenoiseWaveGrad1, DenoiseWaveGrad3, Waveunet2 and Waveunet3 under
- * arch SDDM
+ * Network types: UNetModified2, DenoiseWaveGrad1, DenoiseWaveGrad3, Waveunet, Waveunet2 and Waveunet3
+ * under arch SDDM
  * (with its p_transition / noise_condition args); DiffWave and WaveGrad under arch
  * SDDM_spectrogram.  Any other pairing or type (DenoiseWaveGrad2 among them) returns
  * SDDM_ERR_NOT_IMPLEMENTED.  Waveunet3 is built for the network args of config_waveunet3.json
@@ -70,7 +70,10 @@ void sddm_destroy(sddm_ctx* ctx);
  * refused here with SDDM_ERR_NOT_IMPLEMENTED, not at the first launch.  Waveunet2 likewise is built
  * for the network args of config_waveunet2.json (num_inputs 2, num_channels [24, 48, 72, 96], 5-tap
  * convs, conv_stride 1, 4-tap stride-2 resampling, conv_type "gn", depth 1) and refuses any other
- * value of them with SDDM_ERR_NOT_IMPLEMENTED.  The 1-D networks need no
+ * value of them with SDDM_ERR_NOT_IMPLEMENTED.  Waveunet is built for the network args of
+ * config_waveunet.json (num_inputs 2, the twelve num_channels 24, 48, ..., 288, kernel_size 5, res
+ * "learned", conv_type "gn", depth 1, resample_kernel_size 4, resample_stride 2) and refuses any other
+ * value of them the same way, naming the argument.  The 1-D networks need no
  * num_samples: they take any positive multiple of their hop (see sddm_sample). */
 int sddm_configure(sddm_ctx* ctx, const char* json);
 
@@ -91,7 +94,7 @@ int sddm_missing_params(sddm_ctx* ctx, int64_t* n_missing);
  * equals the same rows of a single-device run.
  * Geometry: UNetModified2 N = num_samples; DiffWave N = 256 frames; WaveGrad N = 300 frames;
  * DenoiseWaveGrad1 N a positive multiple of 400 (2*2*4*5*5); DenoiseWaveGrad3 of 300 (2*2*3*5*5);
- * Waveunet2 and Waveunet3 of 8 (three stride-2 levels).
+ * Waveunet2 and Waveunet3 of 8 (three stride-2 levels); Waveunet of 2048 (eleven).
  * Anything else returns SDDM_ERR_SHAPE before any launch. */
 int sddm_sample(sddm_ctx* ctx, const float* cond, int64_t B, int64_t N, uint64_t seed,
                 int64_t row_offset, float* out, void* stream);
@@ -113,9 +116,9 @@ int sddm_sample_continuous(sddm_ctx* ctx, const float* cond, int64_t B, int64_t 
 
 /* Replaces one noise_estimate_model(condition, x_t, noise_level) call (model.py:110):
  * noise_level: [B] fp32 device.  eps_out: [B, 1, N] fp32 device.  cond is [B, 1, N] for
- * UNetModified2, DenoiseWaveGrad1, DenoiseWaveGrad3, Waveunet2 and Waveunet3 (the noisy waveform; N
+ * UNetModified2, DenoiseWaveGrad1, DenoiseWaveGrad3, Waveunet, Waveunet2 and Waveunet3 (the noisy waveform; N
  * as in sddm_sample) and the spectrogram [B, bins, frames] for DiffWave and WaveGrad.  The output of
- * Waveunet2 and Waveunet3 is clamped to [-1, 1] (waveunet2.py:321-322, waveunet3.py:414-415, eval
+ * Waveunet, Waveunet2 and Waveunet3 is clamped to [-1, 1] (waveunet.py:503-504, waveunet2.py:321-322, waveunet3.py:414-415, eval
  * mode). */
 int sddm_network_forward(sddm_ctx* ctx, const float* cond, const float* x_t,
                          const float* noise_level, int64_t B, int64_t N, float* eps_out,

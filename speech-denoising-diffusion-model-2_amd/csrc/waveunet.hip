@@ -110,7 +110,7 @@ hipError_t launch_wu_stem(int dtype, const WUStemArgs& a, hipStream_t s) { retur
 // kernel; the bias carries the noise constant
 struct Wu3Conv {
   using Args = WUConvArgs;
-  static constexpr bool kPartial = false, kResidual = true;
+  static constexpr bool kPartial = false, kResidual = true, kSplit = false;
   struct Lds { alignas(16) float sc[128]; alignas(16) float sh[128]; };   // 16-byte aligned: transform reads them as b128
   struct Epi { float lvl; };                           // the row's noise level
   struct Row { float bias[4]; };

@@ -10,8 +10,7 @@
 // of 32 or of the 16 rows of a fragment: the policy sets kPartial, so the last 32-channel chunk of
 // the input and the last 16-row fragment of the output are zero-filled where they are staged, never
 // in memory, and stores and statistics are masked to the true Cout.
-#include "wu2_kernels.h"
-#include "wu_conv_impl.h"
+#include "wu2_conv_policy.h"
 
 #include <algorithm>
 
@@ -21,70 +20,10 @@ namespace sddm {
 hipError_t launch_wu2_stem(int dtype, const WUStemArgs& a, hipStream_t s) { return wu_stem_launch<kWu2StemC, false>(dtype, a, s); }
 
 // ---------------- the MFMA convolution: Waveunet2's side of wu_conv_kernel ----------------
-// ReLU(GroupNorm) and the FiLM (fs * v + fh) of one 16-byte unit, rounded to T once
-template <typename T>
-__device__ __forceinline__ f32x4 wu2_transform(f32x4 raw, const float* sc, const float* sh, bool film, f32x4 fs, f32x4 fh) {
-  constexpr int VE = 16 / (int)sizeof(T);
-  typedef T vec __attribute__((ext_vector_type(VE)));
-  vec v = __builtin_bit_cast(vec, raw);
-  const vec s = __builtin_bit_cast(vec, fs), h = __builtin_bit_cast(vec, fh);
-#pragma unroll
-  for (int j = 0; j < VE; ++j) {
-    float y = fmaxf(to_f32<T>(v[j]) * sc[j] + sh[j], 0.f);
-    if (film) y = to_f32<T>(s[j]) * y + to_f32<T>(h[j]);
-    v[j] = from_f32<T>(y);
-  }
-  return __builtin_bit_cast(f32x4, v);
-}
-
-// Cin, Cout multiples of 8; input transform GroupNorm + ReLU + FiLM; no residual paths; the
-// epilogue value is acc + bias, then with enc_dim > 0 leaky_relu(0.2) + the level's encoding
-struct Wu2Conv {
-  using Args = WU2ConvArgs;
-  static constexpr bool kPartial = true, kResidual = false;
-  struct Lds { alignas(16) float sc[96]; alignas(16) float sh[96]; alignas(16) float enc[96]; };   // 16-byte aligned: read as b128
-  struct Epi { int enc; };                             // enc_dim > 0 (an int: a one-byte struct ends up in LDS)
-  struct Row { float bias[4], e4[4]; };
-
-  // PositionalEncoding (waveunet2.py:34-39), fp32 as torch, accurate sinf / cosf
-  static __device__ __forceinline__ void prologue(const Args& a, Lds& l, int b, int tid) {
-    if (a.enc_dim > 0 && tid < a.enc_dim) {
-      const int half = a.enc_dim / 2, k = tid < half ? tid : tid - half;
-      const float arg = wu_level(a.lv, b) * expf(-9.210340371976184f * ((float)k / (float)half));
-      l.enc[tid] = tid < half ? sinf(arg) : cosf(arg);
-    }
-  }
-
-  template <typename T>
-  static __device__ __forceinline__ f32x4 transform(const Args& a, const Lds& l, f32x4 v, int b, int pos, int cq) {
-    const bool film = a.film != nullptr;
-    f32x4 fs = f32x4{0.f, 0.f, 0.f, 0.f}, fh = fs;
-    if (film) {
-      const T* fp = (const T*)a.film + ((size_t)b * a.Lin + pos) * (2 * a.Cin) + cq;
-      fh = *(const f32x4*)fp;
-      fs = *(const f32x4*)(fp + a.Cin);
-    }
-    return wu2_transform<T>(v, l.sc + cq, l.sh + cq, film, fs, fh);
-  }
-
-  static __device__ __forceinline__ Epi epi(const Args& a, int) { return Epi{a.enc_dim > 0 ? 1 : 0}; }
-
-  static __device__ __forceinline__ Row row(const Args& a, const Lds& l, const Epi& e, int cb, bool okc) {
-    Row r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      r.bias[i] = okc ? a.bias[cb + i] : 0.f;
-      r.e4[i] = e.enc && okc ? l.enc[cb + i] : 0.f;
-    }
-    return r;
-  }
-
-  static __device__ __forceinline__ void value(const Epi& e, const Row& r, float* v) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (e.enc) v[i] = (v[i] > 0.f ? v[i] : 0.2f * v[i]) + r.e4[i];
-  }
-
+// Wu2ConvBase (wu2_conv_policy.h): Cin, Cout multiples of 8; input transform GroupNorm + ReLU + FiLM;
+// no residual paths; the epilogue value is acc + bias, then with enc_dim > 0 leaky_relu(0.2) + the
+// level's encoding.  Every launch holds the whole Cout in one block
+struct Wu2Conv : Wu2ConvBase<WU2ConvArgs, 96, false> {
   template <typename T, int MODE>
   static hipError_t launch_nco(const Args& a, dim3 grid, hipStream_t s) {
     // fragments per launch: ConvLayers 24 / 48 / 72 / 96 -> 2 / 3 / 5 / 6 (the resampling layers are 48 / 72 / 96

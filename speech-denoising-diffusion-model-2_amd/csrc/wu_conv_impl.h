@@ -125,6 +125,10 @@ template <> struct WuGeom<WU_UP4> { static constexpr int ROWS = kWuTile / 2 + 2,
 //               multiples of 8): the missing channels are zero-filled where they are staged (LDS, or
 //               the fragment registers in fp32), never in memory, and stores and statistics are
 //               masked to the true Cout.  false: Cin % 32 == 0 and Cout == 16 NCO at compile time
+//   kSplit      the layer's Cout is split over blockIdx.z in groups of Args::gco channels (a multiple
+//               of 16, at most 16 NCO): block z stages its group's weight rows and owns its channels'
+//               stores and statistics; every group stages and transforms the input slab again.
+//               false: one block holds the whole Cout
 //   kResidual   the kernel has Waveunet3's residual paths (Args then has res_mode, res, RC, rw, cond,
 //               x, rw2, shortcut): res_mode == 2 appends the K chunks of a 1x1 conv over `res`
 //               [B][Lout][RC] with the weights rw [Cout][RC] (one tap at the centre row of the slab, no
@@ -154,7 +158,10 @@ __global__ __launch_bounds__(256) void wu_conv_kernel(typename Net::Args a) {
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, l16 = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.y, tile = blockIdx.x;
-  const int Cin = a.Cin, Cout = Net::kPartial ? a.Cout : CP;
+  const int Cin = a.Cin, CoutT = Net::kPartial ? a.Cout : CP;
+  // kSplit: the block computes the channels [co0, co0 + Cout) of the layer's CoutT
+  int co0 = 0, Cout = CoutT;
+  if constexpr (Net::kSplit) { co0 = blockIdx.z * a.gco; Cout = min(CoutT - co0, a.gco); }
   const int ph = MODE == WU_UP4 ? (wave & 1) : 0;
   // first output position of the block (WU_UP4: first input position m0) and first slab row
   const int t0 = MODE == WU_UP4 ? tile * (kWuTile / 2) : tile * kWuTile;
@@ -194,7 +201,7 @@ __global__ __launch_bounds__(256) void wu_conv_kernel(typename Net::Args a) {
 #pragma unroll
     for (int c = 0; c < NCO; ++c) {
       const int co = c * 16 + l16;
-      if (!Net::kPartial || (co < Cout && cg < Cin)) af[c] = load_frag<T>((const char*)(wp + (size_t)co * wstride));
+      if (!Net::kPartial || (co < Cout && cg < Cin)) af[c] = load_frag<T>((const char*)(wp + (size_t)(co0 + co) * wstride));
       else af[c] = Frag<T>{};
     }
   };
@@ -226,6 +233,7 @@ __global__ __launch_bounds__(256) void wu_conv_kernel(typename Net::Args a) {
     if (WL) {                              // weight rows (co, tap) of the chunk, in their global order
       int kwn = KW; const T* wp = (const T*)a.w;
       if constexpr (Net::kResidual) { kwn = main ? KW : 1; wp = main ? (const T*)a.w : (const T*)a.rw; }
+      if constexpr (Net::kSplit) wp += (size_t)co0 * KW * Cin;
 #pragma unroll
       for (int j = 0; j < WIT; ++j) {
         const int u = tid + j * 256, r = u / UPR, q = u - r * UPR;
@@ -325,12 +333,12 @@ __global__ __launch_bounds__(256) void wu_conv_kernel(typename Net::Args a) {
   for (int c = 0; c < NCO; ++c) {
     const int cb = c * 16 + 4 * g;
     const bool okc = !Net::kPartial || cb < Cout;   // Cout % 8 == 0: the 4 channels of an accumulator are in or out together
-    const typename Net::Row row = Net::row(a, lds, epi, cb, okc);
+    const typename Net::Row row = Net::row(a, lds, epi, co0 + cb, okc);
     float s[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       if (ok[p] && okc) {
-        const size_t o = ((size_t)b * a.Lout + opos[p]) * Cout + cb;
+        const size_t o = ((size_t)b * a.Lout + opos[p]) * CoutT + co0 + cb;
         float v[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = acc[c][p][i] + row.bias[i];
@@ -367,7 +375,7 @@ __global__ __launch_bounds__(256) void wu_conv_kernel(typename Net::Args a) {
       for (int i = 0; i < 4; ++i) {
         const float ts = row_sum16(s[i]), tss = row_sum16(ss[i]);
         if (l16 == 0 && okc) {
-          float* st = a.stats + (((size_t)b * nslots + tile * 4 + wave) * Cout + cb + i) * 2;
+          float* st = a.stats + (((size_t)b * nslots + tile * 4 + wave) * CoutT + co0 + cb + i) * 2;
           st[0] = ts;
           st[1] = tss;
         }

@@ -94,9 +94,9 @@ def run(config, model, loader, dataset, device, logger=None, seed=None):
 
 
 def check_num_samples(config):
-    """The waveform-conditioned 1-D networks (DenoiseWaveGrad1 / 3, Waveunet2 and Waveunet3 under arch SDDM)
+    """The waveform-conditioned 1-D networks (DenoiseWaveGrad1 / 3, Waveunet, Waveunet2 and Waveunet3 under arch SDDM)
     resample by fixed factors, so every chunk must be a positive multiple of the network's hop (400 /
-    300 samples; 8 for the three stride-2 levels of Waveunet2 / Waveunet3): fail here, before any data are read,
+    300 samples; 8 for the three stride-2 levels of Waveunet2 / Waveunet3, 2048 for the eleven of Waveunet): fail here, before any data are read,
     rather than in the first batch."""
     cfg = config.config if hasattr(config, "config") else config
     net = getattr(module_network, cfg["network"]["type"], None)

@@ -3,10 +3,12 @@
 WaveGrad and the waveform-conditioned DenoiseWaveGrad1 / DenoiseWaveGrad3 (the reference's
 DenoiseWaveGrad2 has 4 / 8 / 16-channel levels the MFMA convolution cannot take: not built), and
 the 1-D Wave-U-Nets Waveunet2 (FiLM-conditioned, 24 / 48 / 72 / 96 channels: its own MFMA convolution
-for channel counts that are multiples of 8) and Waveunet3, at the arguments of config_waveunet2.json
-and config_waveunet3.json."""
+for channel counts that are multiples of 8), Waveunet (the twelve-level original, 24 ... 288 channels:
+the same convolution with the output channels split over the grid) and Waveunet3, at the arguments of
+config_waveunet2.json, config_waveunet.json and config_waveunet3.json."""
 from .UNetModified2 import UNetModified2  # noqa: F401
 from .diffwave import DiffWave  # noqa: F401
 from .wavegrad import DenoiseWaveGrad1, DenoiseWaveGrad3, WaveGrad  # noqa: F401
+from .waveunet import Waveunet  # noqa: F401
 from .waveunet2 import Waveunet2  # noqa: F401
 from .waveunet3 import Waveunet3  # noqa: F401

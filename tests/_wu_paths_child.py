@@ -1,0 +1,61 @@
+"""Child process of tests/test_gpu_waveunet.py (not a test module).
+
+    python _wu_paths_child.py OUT.npz
+
+The library reads SDDM_WU_NO_FOLD and SDDM_WU_FOLD_ALL when a context is configured, so each path
+is one fresh interpreter with its knob in the environment: SDDM_WU_NO_FOLD=1 sends every layer
+through the per-row kernel (as the default does: it folds at no length), SDDM_WU_FOLD_ALL=1 every
+layer shorter than 128 positions through the batch-folded kernel.  The child runs the facade
+Waveunet with the test weights and writes one npz:
+
+  fw/<dtype>        eps of one forward on the inputs of the golden (B = 2, N = 2048), three dtypes
+  odd/float32       eps at B = 3, N = 6144 (lengths 96 ... 3), the inputs of odd_inputs()
+"""
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+DTYPES = ("float32", "bfloat16", "float16")
+
+
+def odd_inputs():
+    rng = np.random.default_rng(53)
+    B, N = 3, 6144
+    cond = np.clip(0.3 * rng.standard_normal((B, 1, N)), -1, 1).astype(np.float32)
+    x_t = rng.standard_normal((B, 1, N)).astype(np.float32)
+    nl = rng.uniform(0.05, 0.99, B).astype(np.float32)
+    return cond, x_t, nl
+
+
+def main(out_path):
+    sys.path.insert(0, os.path.dirname(HERE))
+    sys.path.insert(0, HERE)
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "speech-denoising-diffusion-model-2_amd"))
+    import torch
+    import model.network as NW
+    import _waveunet_oracle as O
+    from _helpers import golden
+    from _weights import make_params
+
+    params = {k: torch.from_numpy(v) for k, v in make_params(O.param_shapes(), 0).items()}
+    z = golden("waveunet.npz")
+    res = {}
+    for dtype in DTYPES:
+        n = NW.Waveunet(**O.ARGS)
+        n.load_state_dict(params)
+        n.compute_dtype = dtype
+        n = n.cuda()
+        cond, x_t, nl = (torch.from_numpy(z[f"fw/{k}"]).cuda() for k in ("cond", "x_t", "noise_level"))
+        res[f"fw/{dtype}"] = n(cond, x_t, nl).cpu().numpy()
+        if dtype == "float32":
+            cond, x_t, nl = (torch.from_numpy(a).cuda() for a in odd_inputs())
+            res["odd/float32"] = n(cond, x_t, nl).cpu().numpy()
+        del n
+    torch.cuda.synchronize()
+    np.savez(out_path, **res)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1])

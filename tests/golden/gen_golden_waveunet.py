@@ -1,0 +1,116 @@
+"""Generate the Waveunet goldens by running the REFERENCE Python on CPU (build container only).
+
+Usage (from the repo root, with the reference mounted read-only):
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_golden_waveunet.py [--reference /root/reference]
+
+As gen_golden_denoise_wavegrad.py: the reference is imported read-only, its module (built with the
+network args of config_waveunet.json and input_size=-1, stdout captured: the class prints) carries the deterministic weights of ``tests/_weights.py``
+(seed 0) and torch.randn_like / torch.randn are replaced by the Philox stream of ``oracle.philox``
+(draw 0 = x_T, draw t = transition noise at step t, seed 7).  Written: ``waveunet.npz`` (inputs and
+outputs only, no weights), ``waveunet_keys.json`` (state-dict keys and shapes) and
+``reference_config_waveunet.json`` (the settings of config_waveunet.json).
+
+B = 2, N = 2048 (level lengths 2048, 1024, ..., 1: levels 5 to 11 are shorter than a conv tile):
+  fw/{cond,x_t,noise_level,eps}          one forward
+  inf/<noise_condition>/<mode>/{out,steps}  the unmodified SDDM.infer (model.py:50-124) at schedule
+                                         linear, 3, 1e-4, 0.05 with every intermediate x_t
+"""
+import argparse
+import contextlib
+import io
+import json
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(os.path.dirname(HERE))
+SCHED = ("linear", 3, 1e-4, 0.05)
+MODES = ("original", "condition_in", "sr3", "supportive", "conditional")
+B, N = 2, 2048
+
+
+def clamped_share(x):
+    return float(np.mean(np.abs(x) >= 1.0))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reference", default="/root/reference")
+    ap.add_argument("--out", default=HERE)
+    args = ap.parse_args()
+    for p in (HERE, os.path.join(REPO, "tests"), REPO):
+        sys.path.insert(0, p)
+    from gen_golden import NoiseInjector
+    from oracle import philox
+    from _weights import make_params
+    sys.path.insert(0, args.reference)
+    import torch
+    torch.set_num_threads(8)
+    from model.waveunet import Waveunet
+    from model.diffusion import GaussianDiffusion
+    from model.model import SDDM
+
+    with open(os.path.join(args.reference, "config_waveunet.json")) as f:
+        cfg = json.load(f)
+    with contextlib.redirect_stdout(io.StringIO()):
+        net = Waveunet(**cfg["network"]["args"], input_size=-1)
+    shapes = {k: tuple(v.shape) for k, v in net.state_dict().items()}
+    P = make_params(shapes, 0)
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in P.items()})
+    net.eval()
+    out = {}
+    cond = np.clip(0.3 * philox.normal(5, 0, (B, 1, N)), -1, 1).astype(np.float32)
+    x_t = philox.normal(6, 0, (B, 1, N))
+    nl = np.array([0.7, 0.3], dtype=np.float32)
+    with torch.no_grad():
+        eps = net(torch.from_numpy(cond), torch.from_numpy(x_t), torch.from_numpy(nl).reshape(B, 1, 1)).numpy().copy()
+    assert eps.shape == (B, 1, N) and np.isfinite(eps).all()
+    assert len(shapes) == 314 and sum(int(np.prod(s)) for s in shapes.values()) == 12271585
+    # the network clamps its own output: a mostly clamped golden would hide errors
+    assert clamped_share(eps) <= 0.25, f"forward: clamped share {clamped_share(eps)}"
+    out["fw/cond"], out["fw/x_t"], out["fw/noise_level"], out["fw/eps"] = cond, x_t, nl, eps
+    print(f"Waveunet: {sum(int(np.prod(s)) for s in shapes.values())} parameters, {len(shapes)} keys, "
+          f"eps rms {np.sqrt(np.mean(eps ** 2)):.3f}, clamped share {clamped_share(eps):.3f}", flush=True)
+    out["inf/cond"] = cond
+    for nc, modes in (("sqrt_alpha_bar", MODES), ("time_step", ("original",))):
+        for mode in modes:
+            d = GaussianDiffusion(*SCHED, device="cpu")
+            m = SDDM(d, net, noise_condition=nc, p_transition=mode).eval()
+            steps = []
+
+            def rec(fn):
+                def w(*a, **kw):
+                    y = fn(*a, **kw)
+                    steps.append(y.numpy().copy())
+                    return y
+                return w
+            for fn in ("p_transition", "p_transition_sr3", "p_transition_supportive", "p_transition_conditional"):
+                setattr(d, fn, rec(getattr(d, fn)))
+            inj = NoiseInjector(torch, philox, 7)
+            inj.draws = ([] if mode == "supportive" else [0]) + list(range(SCHED[1], 1, -1))
+            with inj, torch.no_grad():
+                y = m.infer(torch.from_numpy(cond)).numpy().copy()
+            steps = np.stack(steps)
+            assert steps.shape == (SCHED[1], B, 1, N) and np.array_equal(steps[-1], y)
+            assert np.isfinite(steps).all()
+            shares = [clamped_share(s) for s in steps]
+            # at most 25 % of a final sample sits at +-1; the intermediates start from x_T ~ N(0, 1)
+            # (31.7 % beyond the clamp) and are held to 35 %, as in gen_golden_denoise_wavegrad.py
+            assert shares[-1] <= 0.25, f"{nc} {mode}: clamped share of the output {shares}"
+            assert max(shares) <= 0.35, f"{nc} {mode}: clamped share {shares}"
+            print(f"{nc} {mode}: clamped share per step {['%.3f' % s for s in shares]}", flush=True)
+            out[f"inf/{nc}/{mode}/out"] = y
+            out[f"inf/{nc}/{mode}/steps"] = steps
+    np.savez_compressed(os.path.join(args.out, "waveunet.npz"), **out)
+    with open(os.path.join(args.out, "waveunet_keys.json"), "w") as f:
+        json.dump([[k, list(s)] for k, s in shapes.items()], f, indent=0)
+    with open(os.path.join(args.out, "reference_config_waveunet.json"), "w") as f:
+        json.dump(cfg, f, indent=4)
+        f.write("\n")
+    print("wrote", os.path.join(args.out, "waveunet.npz"))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,68 @@
+"""GPU: model.model.sharded_infer over Waveunet (the twelve-level Wave-U-Net) in two ranks, as
+tests/test_gpu_multiproc.py does for UNetModified2: the ranks are fresh spawned interpreters that
+share cuda:0 and gather over gloo; an odd batch, so the last rank's shard is padded.  The result
+equals model.infer of the whole batch in this process, bit for bit (bfloat16)."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch.multiprocessing as mp
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+N, B, T = 2048, 3, 3
+
+
+def _paths():
+    sys.path.insert(0, os.path.dirname(HERE))
+    sys.path.insert(0, HERE)
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "speech-denoising-diffusion-model-2_amd"))
+
+
+def _model():
+    import torch
+    import model.diffusion as D
+    import model.model as M
+    import model.network as NW
+    import _waveunet_oracle as O
+    from _weights import make_params
+    dev = torch.device("cuda", 0)
+    net = NW.Waveunet(**O.ARGS)
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in make_params(O.param_shapes(), 0).items()})
+    net.compute_dtype = "bfloat16"
+    m = M.SDDM(D.GaussianDiffusion("linear", T, 1e-4, 0.05, device=dev), net, p_transition="sr3", compute_dtype="bfloat16")
+    return m.to(dev)
+
+
+def _cond():
+    import torch
+    from sddm_hip.synth import noisy_speech
+    return torch.from_numpy(noisy_speech(B, N, seed=977)).cuda()
+
+
+def _rank(rank, world, port, out_path):
+    _paths()
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from model.model import sharded_infer
+    out = sharded_infer(_model(), _cond(), seed=13)
+    if rank == 0:
+        np.save(out_path, out.cpu().numpy())
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_two_ranks_equal_single_run(torch_cuda, tmp_path):
+    import socket
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    sharded = str(tmp_path / "sharded.npy")
+    mp.spawn(_rank, args=(2, port, sharded), nprocs=2, join=True)
+    a = np.load(sharded)
+    b = _model().infer(_cond(), seed=13).cpu().numpy()
+    assert a.shape == (B, 1, N) and np.isfinite(a).all() and float(np.abs(a).max()) > 0
+    assert np.array_equal(a, b)
