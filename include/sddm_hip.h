@@ -60,8 +60,8 @@ void sddm_destroy(sddm_ctx* ctx);
  * parse_config.py:82-95).  `json` is {"arch": {...}, "diffusion": {...}, "network": {...},
  * "num_samples": N} with the reference's type names and args verbatim
  * (config_unet.json, config_diffwave.json, config_wavegrad.json, and the default config.json).
- * Network types: UNetModified2, DenoiseWaveGrad1, DenoiseWaveGrad3, Waveunet, Waveunet2 and Waveunet3
- * under arch SDDM
+ * Network types: UNetModified2, UNetTST, DenoiseWaveGrad1, DenoiseWaveGrad3, Waveunet, Waveunet2 and
+ * Waveunet3 under arch SDDM
  * (with its p_transition / noise_condition args); DiffWave and WaveGrad under arch
  * SDDM_spectrogram.  Any other pairing or type (DenoiseWaveGrad2 among them) returns
  * SDDM_ERR_NOT_IMPLEMENTED.  Waveunet3 is built for the network args of config_waveunet3.json
@@ -73,7 +73,10 @@ void sddm_destroy(sddm_ctx* ctx);
  * value of them with SDDM_ERR_NOT_IMPLEMENTED.  Waveunet is built for the network args of
  * config_waveunet.json (num_inputs 2, the twelve num_channels 24, 48, ..., 288, kernel_size 5, res
  * "learned", conv_type "gn", depth 1, resample_kernel_size 4, resample_stride 2) and refuses any other
- * value of them the same way, naming the argument.  The 1-D networks need no
+ * value of them the same way, naming the argument.  UNetTST (config_unettst.json) takes
+ * UNetModified2's arguments and n_TSTB >= 1; it needs inner_channel 32, a bottom level of 160
+ * channels (channel_mults ending in 5) and at most 64 bottom-level positions (num_samples up to
+ * 32832 at the config's framing), and refuses anything else here.  The 1-D networks need no
  * num_samples: they take any positive multiple of their hop (see sddm_sample). */
 int sddm_configure(sddm_ctx* ctx, const char* json);
 
@@ -123,6 +126,14 @@ int sddm_sample_continuous(sddm_ctx* ctx, const float* cond, int64_t B, int64_t 
 int sddm_network_forward(sddm_ctx* ctx, const float* cond, const float* x_t,
                          const float* noise_level, int64_t B, int64_t N, float* eps_out,
                          void* stream);
+
+/* Replaces one Dual_Transformer(160, 160, 0, n_TSTB).forward(input) call (model/UNetTST.py:212-233) on
+ * a context configured for network UNetTST: in, out [B, 160, dim2, dim1] fp32 device (NCHW, as the
+ * reference module takes it).  Only the context's mid.* parameters need to be loaded.  The block runs
+ * in the context's compute dtype, so in a 16-bit context the input and the output are rounded to it.
+ * dim2 * dim1 above 64 returns SDDM_ERR_NOT_IMPLEMENTED.  Returns after the result is complete. */
+int sddm_dual_transformer(sddm_ctx* ctx, const float* in, int64_t B, int64_t dim2, int64_t dim1,
+                          float* out, void* stream);
 
 /* Replaces diffusion.p_transition*(x_t, t, predicted[, condition]) (diffusion.py:164-223).
  * cond may be NULL for modes that do not read it. */

@@ -18,6 +18,7 @@ struct EmbedArgs {
   const float* pw; const float* pb;  // concatenated FeatureWiseAffine Linears [SC][dim], [SC] (+conv1 bias)
   int SC;                     // sum of projected channels
   float* out;                 // [R][SC]
+  int no_final_swish;         // 1: Linear -> Swish -> Linear (UNetTST.py:293-298), no Swish after the second Linear
 };
 hipError_t launch_embed(const EmbedArgs& a, hipStream_t s);
 
@@ -30,6 +31,18 @@ struct GNArgs {
   float* scale; float* shift; // [B][Ca+Cb]
 };
 hipError_t launch_gn_finalize(const GNArgs& a, hipStream_t s);
+
+// ---- torch.cat((x, skip), dim=1) made real (UNetModified2.py:263) ----
+// The conv kernels read a concatenation virtually and finalize its GroupNorm per source, which needs
+// every group inside one source.  Where a group would straddle the two (GroupNorm(32, 128 + 160)),
+// this copies them into one tensor with per-tile statistics of its own, and the conv reads that.
+struct ConcatArgs {
+  const void* a; const void* b; int CA, CB;   // [B][P][CA], [B][P][CB] (T)
+  void* out;                  // [B][P][CA + CB] (T)
+  float* stats;               // [B][P / n_tile][CA + CB][2] (sum, M2 about the tile mean)
+  int P, n_tile;              // pixels per image, pixels per statistics tile (divides P)
+};
+hipError_t launch_concat(int dtype, const ConcatArgs& a, int B, hipStream_t s);
 
 // ---- framing + first Conv2d(2 -> C) (UNetModified2.py:23-28, 177-178, 244-247) ----
 struct ConvInArgs {

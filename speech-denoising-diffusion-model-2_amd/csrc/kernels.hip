@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void embed_kernel(EmbedArgs a) {
   for (int i = tid; i < D; i += blockDim.x) {
     float s = a.b2[i];
     for (int j = 0; j < D4; ++j) s += a.w2[i * D4 + j] * h1[j];
-    h2[i] = s / (1.0f + expf(-s));
+    h2[i] = a.no_final_swish ? s : s / (1.0f + expf(-s));
   }
   __syncthreads();
   for (int c = tid; c < a.SC; c += blockDim.x) {
@@ -123,6 +123,49 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(GNArgs a) {
 
 hipError_t launch_gn_finalize(const GNArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(a.G, a.B), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// =============================================================================================
+// Concatenation of two activation tensors along the channels, with the per-tile statistics of the
+// result (ConcatArgs).  One block per (statistics tile, image): the copy, then one thread per
+// channel sums its n_tile pixels in pixel order (two passes), so the statistics depend on the
+// image alone.
+// =============================================================================================
+template <typename T>
+__global__ __launch_bounds__(256) void concat_kernel(ConcatArgs a) {
+  const int tile = blockIdx.x, b = blockIdx.y, C = a.CA + a.CB, tiles = a.P / a.n_tile;
+  const size_t p0 = (size_t)b * a.P + (size_t)tile * a.n_tile;
+  const T* sa = (const T*)a.a + p0 * a.CA;
+  const T* sb = (const T*)a.b + p0 * a.CB;
+  T* o = (T*)a.out + p0 * C;
+  for (int i = threadIdx.x; i < a.n_tile * C; i += blockDim.x) {
+    const int p = i / C, c = i - p * C;
+    o[i] = c < a.CA ? sa[p * a.CA + c] : sb[p * a.CB + c - a.CA];
+  }
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    const T* src = c < a.CA ? sa + c : sb + (c - a.CA);
+    const int ld = c < a.CA ? a.CA : a.CB;
+    float s = 0.f;
+    for (int p = 0; p < a.n_tile; ++p) s += to_f32<T>(src[p * ld]);
+    const float mean = s / (float)a.n_tile;
+    float m2 = 0.f;
+    for (int p = 0; p < a.n_tile; ++p) {
+      const float d = to_f32<T>(src[p * ld]) - mean;
+      m2 += d * d;
+    }
+    float* dst = a.stats + (((size_t)b * tiles + tile) * C + c) * 2;
+    dst[0] = s;
+    dst[1] = m2;
+  }
+}
+
+hipError_t launch_concat(int dtype, const ConcatArgs& a, int B, hipStream_t s) {
+  if (B < 1 || a.CA < 1 || a.CB < 1 || a.P < 1 || a.n_tile < 1 || a.P % a.n_tile) return hipErrorInvalidValue;
+  const dim3 grid(a.P / a.n_tile, B), blk(256);
+  if (dtype == DT_BF16) hipLaunchKernelGGL(concat_kernel<bf16_t>, grid, blk, 0, s, a);
+  else if (dtype == DT_F16) hipLaunchKernelGGL(concat_kernel<f16_t>, grid, blk, 0, s, a);
+  else hipLaunchKernelGGL(concat_kernel<float>, grid, blk, 0, s, a);
   return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // libsddm_hip runtime: context, parameter registry, weight packer (WeightPacker) and the C ABI
 // declared in include/sddm_hip.h, over six network paths:
 //   UNetModified2        this file: the per-batch plan of one reverse step, run in lanes whose step
-//                        graphs replay concurrently (build_plan, sample_impl)
+//                        graphs replay concurrently (build_plan, sample_impl); UNetTST is the same
+//                        plan with the Dual_Transformer op (dual_transformer.h) in place of mid.0
 //   DiffWave             dw_runtime.h  \
 //   WaveGrad, DenoiseWaveGrad1 / 3  wg_runtime.h   >  sequential networks: each implements SeqNet, and
 //   Waveunet3            wu_runtime.h  |   seq_sample / seq_forward here drive whichever is configured
@@ -32,6 +33,7 @@
 #include "../../include/sddm_hip.h"
 #include "json_mini.h"
 #include "kernels.h"
+#include "dual_transformer.h"
 #include "q_kernels.h"
 #include "stft_kernels.h"
 #include "sddm_common.h"
@@ -122,8 +124,10 @@ struct UNetCfg {
   std::vector<int> mults{1, 2, 3, 4, 5};
   int seg = 128, stride = 64;
   double dropout = 0.0;
+  int mid_tst = 0;   // 1: UNetTST -- mid is Dual_Transformer(C, C, 0, n_tstb) (UNetTST.py:324), and the
+  int n_tstb = 6;    //    noise MLP has no final Swish (UNetTST.py:293-298)
 };
-struct LayerDesc { int kind; std::string name; int cin, cout; };  // kind 0 conv,1 res,2 down,3 up,4 final
+struct LayerDesc { int kind; std::string name; int cin, cout; };  // kind 0 conv,1 res,2 down,3 up,4 final,5 dual transformer
 static std::vector<LayerDesc> unet_layers(const UNetCfg& c, std::vector<LayerDesc>* downs_out,
                                           std::vector<LayerDesc>* mid_out, std::vector<LayerDesc>* ups_out) {
   std::vector<LayerDesc> downs, mid, ups;
@@ -140,7 +144,8 @@ static std::vector<LayerDesc> unet_layers(const UNetCfg& c, std::vector<LayerDes
     downs.push_back({2, "downs." + std::to_string(idx++), cout, cout});
     feat.push_back(cout);
   }
-  mid.push_back({1, "mid.0", cin, cin});
+  if (c.mid_tst) mid.push_back({5, "mid", cin, cin});
+  else mid.push_back({1, "mid.0", cin, cin});
   idx = 0;
   for (int ind = (int)c.mults.size() - 1; ind >= 0; --ind) {
     cin = c.inner * c.mults[ind];
@@ -196,6 +201,37 @@ static std::map<std::string, std::vector<int64_t>> unet_param_shapes(const UNetC
     } else if (L.kind == 0) {
       s[n + ".weight"] = {L.cout, L.cin, 3, 3};
       s[n + ".bias"] = {L.cout};
+    } else if (L.kind == 5) {   // Dual_Transformer (UNetTST.py:184-210), d = C / 2
+      const int64_t C = L.cin, d = C / 2;
+      s[n + ".input.0.weight"] = {d, C, 1, 1};
+      s[n + ".input.0.bias"] = {d};
+      s[n + ".input.1.weight"] = {1};
+      s[n + ".output.0.weight"] = {C, d, 1, 1};
+      s[n + ".output.0.bias"] = {C};
+      s[n + ".output.1.weight"] = {1};
+      for (int i = 0; i < c.n_tstb; ++i)
+        for (const char* pass : {"row", "col"}) {
+          const std::string e = n + "." + pass + "_trans." + std::to_string(i);
+          s[e + ".self_attn.in_proj_weight"] = {3 * d, d};
+          s[e + ".self_attn.in_proj_bias"] = {3 * d};
+          s[e + ".self_attn.out_proj.weight"] = {d, d};
+          s[e + ".self_attn.out_proj.bias"] = {d};
+          for (const char* sfx : {"", "_reverse"}) {
+            s[e + ".gru.weight_ih_l0" + sfx] = {6 * d, d};
+            s[e + ".gru.weight_hh_l0" + sfx] = {6 * d, 2 * d};
+            s[e + ".gru.bias_ih_l0" + sfx] = {6 * d};
+            s[e + ".gru.bias_hh_l0" + sfx] = {6 * d};
+          }
+          s[e + ".linear2.weight"] = {d, 4 * d};
+          s[e + ".linear2.bias"] = {d};
+          for (const char* nm : {".norm1", ".norm2"}) {
+            s[e + nm + ".weight"] = {d};
+            s[e + nm + ".bias"] = {d};
+          }
+          const std::string gn = n + "." + pass + "_norm." + std::to_string(i);
+          s[gn + ".weight"] = {d};
+          s[gn + ".bias"] = {d};
+        }
     } else {
       s[n + ".block.0.weight"] = {L.cin};
       s[n + ".block.0.bias"] = {L.cin};
@@ -480,6 +516,52 @@ static int upload_weights(sddm_ctx* c) {
     } else if (L.kind == 2 || L.kind == 3) {
       add_conv3(n + ".w", P(n + ".conv.weight"));
       add_f32(n + ".b", P(n + ".conv.bias").data);
+    } else if (L.kind == 5) {
+      // Dual_Transformer: every matrix as MFMA A fragments in the compute dtype, every vector in
+      // fp32, at the offsets of dual_transformer.h
+      const int ne = 2 * c->ucfg.n_tstb;
+      char* wm = pk.raw(n + ".wmat", ((size_t)kTstWEnc0 + (size_t)ne * kTstEncW) * es);
+      std::vector<float> wv((size_t)kTstVEnc0 + (size_t)ne * kTstEncV, 0.f);
+      auto frag = [&](size_t off, const Param& w, int N, int K) {   // W[N][K] -> [N/16][ceil(K/32)][64][8]
+        const int KC = (K + 31) / 32;
+        for (int o = 0; o < N; ++o)
+          for (int k = 0; k < K; ++k)
+            store_elem(wm, off + ((size_t)((o / 16) * KC + k / 32) * 64 + (o % 16) + 16 * ((k % 32) / 8)) * 8 + k % 8,
+                       w.data[(size_t)o * K + k], dt);
+      };
+      auto vec = [&](size_t off, const Param& v) { std::copy(v.data.begin(), v.data.end(), wv.begin() + off); };
+      frag(kTstWIn, P(n + ".input.0.weight"), kTstD, kTstC);
+      frag(kTstWOut, P(n + ".output.0.weight"), kTstC, kTstD);
+      vec(kTstVInB, P(n + ".input.0.bias"));
+      vec(kTstVInA, P(n + ".input.1.weight"));
+      vec(kTstVOutB, P(n + ".output.0.bias"));
+      vec(kTstVOutA, P(n + ".output.1.weight"));
+      for (int e = 0; e < ne; ++e) {
+        const char* pass = e % 2 ? "col" : "row";
+        const std::string p = n + "." + pass + "_trans." + std::to_string(e / 2);
+        const std::string gn = n + "." + pass + "_norm." + std::to_string(e / 2);
+        const size_t wo = (size_t)kTstWEnc0 + (size_t)e * kTstEncW, vo = (size_t)kTstVEnc0 + (size_t)e * kTstEncV;
+        frag(wo + kTstEInProj, P(p + ".self_attn.in_proj_weight"), 3 * kTstD, kTstD);
+        frag(wo + kTstEOutProj, P(p + ".self_attn.out_proj.weight"), kTstD, kTstD);
+        for (int d = 0; d < 2; ++d) {
+          const std::string sfx = d ? "_reverse" : "";
+          frag(wo + kTstEIh + (size_t)d * kTstEIhSize, P(p + ".gru.weight_ih_l0" + sfx), 3 * kTstHid, kTstD);
+          frag(wo + kTstEHh + (size_t)d * kTstEHhSize, P(p + ".gru.weight_hh_l0" + sfx), 3 * kTstHid, kTstHid);
+          vec(vo + kTstVBih + 960 * d, P(p + ".gru.bias_ih_l0" + sfx));
+          vec(vo + kTstVBhh + 960 * d, P(p + ".gru.bias_hh_l0" + sfx));
+        }
+        frag(wo + kTstELin2, P(p + ".linear2.weight"), kTstD, 2 * kTstHid);
+        vec(vo + kTstVInProjB, P(p + ".self_attn.in_proj_bias"));
+        vec(vo + kTstVOutProjB, P(p + ".self_attn.out_proj.bias"));
+        vec(vo + kTstVLn1W, P(p + ".norm1.weight"));
+        vec(vo + kTstVLn1B, P(p + ".norm1.bias"));
+        vec(vo + kTstVLin2B, P(p + ".linear2.bias"));
+        vec(vo + kTstVLn2W, P(p + ".norm2.weight"));
+        vec(vo + kTstVLn2B, P(p + ".norm2.bias"));
+        vec(vo + kTstVGnW, P(gn + ".weight"));
+        vec(vo + kTstVGnB, P(gn + ".bias"));
+      }
+      add_f32(n + ".wvec", wv);
     } else {
       add_f32(n + ".gamma", P(n + ".block.0.weight").data);
       add_f32(n + ".beta", P(n + ".block.0.bias").data);
@@ -612,13 +694,17 @@ static bool choose_deep(int dt, int B, ConvArgs a, bool s2, ConvChoice& ch, int 
   a.deep_nb = nb;
   struct Cand { int mt, nw, TR, TW, tiles_x, n_tiles, blocks, rounds; };
   std::vector<Cand> cs;
+  // second pass, only when the first finds nothing (frame counts such as 96, whose 6 x 8 level no
+  // full tile divides): partly filled tiles of the most rows that divide the image
+  for (int pass = 0; pass < 2 && cs.empty(); ++pass)
   for (int mt : {128, 64, 32, 16}) {
     if (mt == 16 && nb != 16) continue;
     const int TW = std::min(a.Wo, mt);
     if (mt % TW || a.Wo % TW) continue;
-    const int TR = std::min(mt / TW, a.Ho);
+    int TR = std::min(mt / TW, a.Ho);
+    while (pass == 1 && a.Ho % TR) --TR;
     if (a.Ho % TR) continue;
-    if (TR * TW < mt && mt > 32) continue;        // partial tiles only at the smallest size
+    if (TR * TW < mt && mt > 32 && pass == 0) continue;   // partial tiles only at the smallest size
     a.TR = TR; a.TW = TW; a.tiles_x = a.Wo / TW; a.n_tiles = a.tiles_x * (a.Ho / TR);
     for (int nw : {8, 4}) {
       a.deep_nw = nw;
@@ -776,7 +862,7 @@ static int build_lane(sddm_ctx* c, Lane& L) {
   L.off_cond = A.reserve(sizeof(float) * (size_t)B * N);
   L.off_x = A.reserve(sizeof(float) * (size_t)B * N);
 
-  enum { ST_CONVIN, ST_GN, ST_CONV, ST_FINAL };
+  enum { ST_CONVIN, ST_GN, ST_CONV, ST_FINAL, ST_TST, ST_CAT };
   struct Step {
     int type = 0;
     std::string w;          // weight-name prefix
@@ -816,7 +902,7 @@ static int build_lane(sddm_ctx* c, Lane& L) {
     }
     // "chain": the layer runs inside the bottom-level chain launch; its tensor keeps the tiling the
     // heuristic would give it (only the chain reads or writes it)
-    const bool chain = kind == 4 && dt != DT_F32;
+    const bool chain = kind == 4 && dt != DT_F32 && !u.mid_tst;   // UNetTST has no mid.0: a table's chain marks are ignored
     if (kind == 4) kind = 0;
     const bool ok = choose_conv(dt, PB, Cin, RC, res_mode, Ho, Wo, cout, s2, up, ch, wm, wn, kind, ka, wb);
     ch.chain = chain ? 1 : 0;
@@ -833,9 +919,21 @@ static int build_lane(sddm_ctx* c, Lane& L) {
     ConvChoice c1, c2;
     if (!pick(n + ".block1", cin, 0, 0, H, Wd, cout, false, false, c1)) return -1;
     if (!pick(n + ".block2", cout, cin, cin != cout ? 2 : 1, H, Wd, cout, false, false, c2)) return -1;
-    const int g1 = new_gn(xa, xb, n + ".block1");
+    // block1's GroupNorm is finalized per source of cat(x, skip); where a group would straddle the
+    // two (res_blocks >= 2: GroupNorm(32, 128 + 160)), the concatenation is made real first
+    // (ConcatArgs) and block1 reads that one tensor.  The res_conv keeps the two raw sources
+    int ga = xa, gb = xb;
+    if (xb >= 0 && u.groups > 0 && cin % u.groups == 0 && tres[xa].C % (cin / u.groups)) {
+      int nt = std::min(H * Wd, 256);
+      while ((H * Wd) % nt) --nt;
+      const int m = new_tensor(cin, H, Wd, H * Wd / nt, nt);
+      Step st; st.type = ST_CAT; st.w = n + ".cat"; st.srcA = xa; st.srcB = xb; st.out = m;
+      prog.push_back(st);
+      ga = m; gb = -1;
+    }
+    const int g1 = new_gn(ga, gb, n + ".block1");
     const int h = new_tensor(cout, H, Wd, c1.n_tiles, c1.TR * c1.TW);
-    { Step st; st.type = ST_CONV; st.w = n + ".block1"; st.rb = n; st.srcA = xa; st.srcB = xb; st.gn = g1;
+    { Step st; st.type = ST_CONV; st.w = n + ".block1"; st.rb = n; st.srcA = ga; st.srcB = gb; st.gn = g1;
       st.out = h; st.cout = cout; st.temb = true; st.ch = c1; prog.push_back(st); }
     const int g2 = new_gn(h, -1, n + ".block2");
     const int o = new_tensor(cout, H, Wd, c2.n_tiles, c2.TR * c2.TW);
@@ -865,6 +963,17 @@ static int build_lane(sddm_ctx* c, Lane& L) {
     feats.push_back(cur);
   }
   for (const LayerDesc& L : mid) {
+    if (L.kind == 5) {
+      // Dual_Transformer in place of mid.0: one launch, one block and one statistics tile per image
+      const int H = tres[cur].H, Wd = tres[cur].W;
+      if (L.cin != kTstC || H * Wd > kTstMaxTokens)
+        FAIL(SDDM_ERR_NOT_IMPLEMENTED, "Dual_Transformer at %d channels, %d x %d tokens", L.cin, H, Wd);
+      const int o = new_tensor(L.cout, H, Wd, 1, H * Wd);
+      Step st; st.type = ST_TST; st.w = L.name; st.srcA = cur; st.out = o; st.cout = L.cout;
+      prog.push_back(st);
+      cur = o;
+      continue;
+    }
     cur = res_block(L.name, cur, -1, L.cin, L.cout);
     if (cur < 0) FAIL(SDDM_ERR_SHAPE, "no tile for %s", L.name.c_str());
   }
@@ -997,7 +1106,31 @@ static int build_lane(sddm_ctx* c, Lane& L) {
       si += 4;
       continue;
     }
-    if (st.type == ST_CONVIN) {
+    if (st.type == ST_CAT) {
+      const Tensor sa = TT(st.srcA), sb = TT(st.srcB), o = TT(st.out);
+      ConcatArgs a{};
+      a.a = sa.p; a.b = sb.p; a.CA = sa.C; a.CB = sb.C; a.out = o.p; a.stats = o.stats;
+      a.P = o.H * o.W; a.n_tile = o.n_tile;
+      const double bytes = 2.0 * B * a.P * o.C * es;
+      L.ops.push_back({4, bytes, 0.0, [a, dt, B](hipStream_t s) { return launch_concat(dt, a, B, s); }, st.w});
+      L.ops.back().kname = std::string("concat_kernel<") + dt_name(dt) + ">";
+      L.ops.back().kinst = L.ops.back().kname;
+    } else if (st.type == ST_TST) {
+      const Tensor src = TT(st.srcA), o = TT(st.out);
+      DualTransformerArgs a{};
+      a.x = src.p; a.out = o.p; a.stats = o.stats;
+      a.wmat = WV(st.w + ".wmat"); a.wvec = WF(st.w + ".wvec");
+      a.dim2 = src.H; a.dim1 = src.W; a.n_tstb = u.n_tstb;
+      const int ne = 2 * u.n_tstb;
+      const double P = (double)src.H * src.W;
+      const double bytes = 2.0 * B * P * kTstC * es + ((double)kTstWEnc0 + (double)ne * kTstEncW) * es;
+      const double flops = 2.0 * B * P * (2.0 * kTstC * kTstD + ne * (4.0 * kTstD * kTstD + 2.0 * 3 * kTstHid * (kTstD + kTstHid) +
+                                                                   2.0 * kTstHid * kTstD));
+      L.ops.push_back({4, bytes, flops, [a, dt, B](hipStream_t s) { return launch_dual_transformer(dt, a, B, s); },
+                       st.w + "[dual_transformer]"});
+      L.ops.back().kname = std::string("dual_transformer_kernel<") + dt_name(dt) + ">";
+      L.ops.back().kinst = L.ops.back().kname;
+    } else if (st.type == ST_CONVIN) {
       ConvInArgs a{};
       a.N = N; a.F = F; a.W = W; a.S = S; a.Cout = u.inner;
       a.w = WF("downs.0.weight"); a.bias = WF("downs.0.bias");
@@ -1414,8 +1547,10 @@ int sddm_configure(sddm_ctx* c, const char* json) {
     const auto shapes = wu1_param_shapes(us->net);
     return finish_configure(c, T, tabs, shapes, std::move(us), -1);
   }
-  if (c->net_type != "UNetModified2") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "network type '%s'", c->net_type.c_str());
-  if (c->arch_type != "SDDM") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "UNetModified2 under arch '%s'", c->arch_type.c_str());
+  // UNetTST (UNetTST.py:270-392): UNetModified2 with mid = Dual_Transformer and no final Swish in the noise MLP
+  const bool tst = c->net_type == "UNetTST";
+  if (c->net_type != "UNetModified2" && !tst) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "network type '%s'", c->net_type.c_str());
+  if (c->arch_type != "SDDM") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "%s under arch '%s'", c->net_type.c_str(), c->arch_type.c_str());
   const Json& na = net.at("args");
   UNetCfg u;
   u.in_channel = (int)na.number("in_channel", 2);
@@ -1436,6 +1571,28 @@ int sddm_configure(sddm_ctx* c, const char* json) {
   const int div = 1 << (int)u.mults.size();
   if (F % div || u.seg % div) FAIL(SDDM_ERR_SHAPE, "n_frames %d and segment_len %d must be multiples of %d", F, u.seg, div);
   if (u.seg % u.stride) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "segment_len %% segment_stride != 0");
+  if (tst) {   // everything the plan or the Dual_Transformer kernel would refuse later is refused here
+    u.mid_tst = 1;
+    u.n_tstb = (int)na.number("n_TSTB", 6);
+    if (u.n_tstb < 1) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "n_TSTB %d: at least one transformer block", u.n_tstb);
+    if (u.res_blocks < 1) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "res_blocks %d: at least one", u.res_blocks);
+    if (u.inner != 32 || 512 % u.seg)
+      FAIL(SDDM_ERR_NOT_IMPLEMENTED, "inner_channel %d / segment_len %d: conv_in needs 32 and a divisor of 512", u.inner, u.seg);
+    const int Cb = u.mults.empty() ? 0 : u.inner * u.mults.back();
+    if (Cb != kTstC)
+      FAIL(SDDM_ERR_NOT_IMPLEMENTED, "channel_mults: the bottom level has %d channels, the Dual_Transformer kernel is built for %d",
+           Cb, kTstC);
+    if ((Cb / 2) % kTstHeads) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "channel_mults: %d heads do not divide d_model %d", kTstHeads, Cb / 2);
+    if (u.groups < 1 || 256 % u.groups)
+      FAIL(SDDM_ERR_NOT_IMPLEMENTED, "norm_groups %d: the GroupNorm finalize needs a divisor of 256", u.groups);
+    for (int m : u.mults)
+      if (m < 1 || (u.inner * m) % u.groups)
+        FAIL(SDDM_ERR_NOT_IMPLEMENTED, "channel_mults / norm_groups: %d channels in groups of %d", u.inner * m, u.groups);
+    const int tok = (F / div) * (u.seg / div);
+    if (tok > kTstMaxTokens)
+      FAIL(SDDM_ERR_NOT_IMPLEMENTED, "num_samples %d: the bottom level has %d x %d = %d tokens, the Dual_Transformer kernel holds %d",
+           Ns, F / div, u.seg / div, tok, kTstMaxTokens);
+  }
   c->ucfg = u;
   return finish_configure(c, T, tabs, unet_param_shapes(u), nullptr, Ns);
 }
@@ -1547,7 +1704,7 @@ static int sample_impl(sddm_ctx* c, const float* cond, int64_t B, int64_t N, uin
   e.w1 = c->warena.at<float>(c->woff.at("mlp.w1")); e.b1 = c->warena.at<float>(c->woff.at("mlp.b1"));
   e.w2 = c->warena.at<float>(c->woff.at("mlp.w2")); e.b2 = c->warena.at<float>(c->woff.at("mlp.b2"));
   e.pw = c->warena.at<float>(c->woff.at("proj.w")); e.pb = c->warena.at<float>(c->woff.at("proj.b"));
-  e.SC = c->SC; e.out = temb_tab;
+  e.SC = c->SC; e.out = temb_tab; e.no_final_swish = c->ucfg.mid_tst;
   SDDM_HIP_CHECK(launch_embed(e, user));
   // per-lane state: x_t (graph-stable copy when replaying graphs), condition rows, step counter
   for (auto& Lp : c->lanes) {
@@ -1655,7 +1812,7 @@ int sddm_network_forward(sddm_ctx* c, const float* cond, const float* x_t, const
     e.w1 = c->warena.at<float>(c->woff.at("mlp.w1")); e.b1 = c->warena.at<float>(c->woff.at("mlp.b1"));
     e.w2 = c->warena.at<float>(c->woff.at("mlp.w2")); e.b2 = c->warena.at<float>(c->woff.at("mlp.b2"));
     e.pw = c->warena.at<float>(c->woff.at("proj.w")); e.pb = c->warena.at<float>(c->woff.at("proj.b"));
-    e.SC = c->SC; e.out = temb;
+    e.SC = c->SC; e.out = temb; e.no_final_swish = c->ucfg.mid_tst;
     SDDM_HIP_CHECK(launch_embed(e, s));
     L.rs.cond = cond + off; L.rs.x = const_cast<float*>(x_t) + off; L.rs.temb = temb; L.rs.temb_per_b = 1;
     L.rs.t_dev = nullptr; L.rs.final_mode = -1; L.rs.eps_out = eps_out + off; L.rs.seed = 0; L.rs.row_offset = 0;
@@ -1663,6 +1820,43 @@ int sddm_network_forward(sddm_ctx* c, const float* cond, const float* x_t, const
     r = run_ops(c, L, s);
     if (r) return r;
   }
+  return SDDM_OK;
+}
+
+// The Dual_Transformer of a UNetTST context alone (UNetTST.py:212-233).  Only the mid.* parameters
+// need to be loaded: parameters outside mid that are still missing are packed as zeros
+int sddm_dual_transformer(sddm_ctx* c, const float* in, int64_t B, int64_t dim2, int64_t dim1, float* out, void* stream) {
+  if (!c || !c->configured) FAIL(SDDM_ERR_STATE, "context not configured");
+  if (c->net_type != "UNetTST") FAIL(SDDM_ERR_STATE, "sddm_dual_transformer needs a context configured for UNetTST");
+  if (!in || !out) FAIL(SDDM_ERR_INVALID_ARG, "NULL tensor");
+  if (B < 1 || B > 65535 || dim2 < 1 || dim1 < 1) FAIL(SDDM_ERR_INVALID_ARG, "shape B=%lld dim2=%lld dim1=%lld", (long long)B, (long long)dim2, (long long)dim1);
+  if (dim2 * dim1 > kTstMaxTokens)
+    FAIL(SDDM_ERR_NOT_IMPLEMENTED, "dim2 * dim1 = %lld tokens: the Dual_Transformer kernel holds %d", (long long)(dim2 * dim1), kTstMaxTokens);
+  SDDM_HIP_CHECK(hipSetDevice(c->device));
+  for (auto& kv : c->params) {
+    if (kv.second.loaded) continue;
+    if (kv.first.rfind("mid.", 0) == 0) FAIL(SDDM_ERR_STATE, "parameter %s not loaded", kv.first.c_str());
+    int64_t n = 1;
+    for (int64_t d : kv.second.shape) n *= d;
+    if ((int64_t)kv.second.data.size() != n) kv.second.data.assign((size_t)n, 0.f);
+  }
+  if (c->params_dirty) TRY(upload_weights(c));
+  if (c->tables_dirty) TRY(upload_tables(c));
+  hipStream_t s = (hipStream_t)stream;
+  const int P = (int)(dim2 * dim1);
+  const size_t bytes = (size_t)B * P * kTstC * dtype_size(c->dtype);
+  char* buf = nullptr;
+  SDDM_HIP_CHECK(hipMalloc(&buf, 2 * bytes));
+  DualTransformerArgs a{};
+  a.x = buf; a.out = buf + bytes; a.stats = nullptr;
+  a.wmat = c->warena.base + c->woff.at("mid.wmat"); a.wvec = c->warena.at<float>(c->woff.at("mid.wvec"));
+  a.dim2 = (int)dim2; a.dim1 = (int)dim1; a.n_tstb = c->ucfg.n_tstb;
+  hipError_t e = launch_dt_pack(c->dtype, in, buf, (int)B, kTstC, P, s);
+  if (e == hipSuccess) e = launch_dual_transformer(c->dtype, a, (int)B, s);
+  if (e == hipSuccess) e = launch_dt_unpack(c->dtype, buf + bytes, out, (int)B, kTstC, P, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(buf);
+  if (e != hipSuccess) FAIL(SDDM_ERR_HIP, "dual_transformer: %s", hipGetErrorString(e));
   return SDDM_OK;
 }
 

@@ -5,8 +5,12 @@ DenoiseWaveGrad2 has 4 / 8 / 16-channel levels the MFMA convolution cannot take:
 the 1-D Wave-U-Nets Waveunet2 (FiLM-conditioned, 24 / 48 / 72 / 96 channels: its own MFMA convolution
 for channel counts that are multiples of 8), Waveunet (the twelve-level original, 24 ... 288 channels:
 the same convolution with the output channels split over the grid) and Waveunet3, at the arguments of
-config_waveunet2.json, config_waveunet.json and config_waveunet3.json."""
+config_waveunet2.json, config_waveunet.json and config_waveunet3.json.  UNetTST (config_unettst.json) is
+UNetModified2 with the dual-path transformer block Dual_Transformer (multi-head attention and a
+bidirectional GRU along the rows, then along the columns of the bottom level) in place of ``mid``; the
+block is also a module of its own.  The reference's CAUNet, TSTNN and SNR-estimator networks are not built."""
 from .UNetModified2 import UNetModified2  # noqa: F401
+from .UNetTST import Dual_Transformer, UNetTST  # noqa: F401
 from .diffwave import DiffWave  # noqa: F401
 from .wavegrad import DenoiseWaveGrad1, DenoiseWaveGrad3, WaveGrad  # noqa: F401
 from .waveunet import Waveunet  # noqa: F401

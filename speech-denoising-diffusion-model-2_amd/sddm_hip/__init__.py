@@ -24,7 +24,7 @@ TABLE_NAMES = ("betas", "alphas", "alpha_bar", "sqrt_alpha_bar", "predicted_nois
                "sqrt_delta_estimated")
 EXPORTS = ("sddm_abi_version", "sddm_last_error", "sddm_create", "sddm_destroy", "sddm_configure",
            "sddm_load_param", "sddm_missing_params", "sddm_sample", "sddm_sample_noise", "sddm_sample_continuous",
-           "sddm_network_forward",
+           "sddm_network_forward", "sddm_dual_transformer",
            "sddm_transition", "sddm_q_sample", "sddm_log_spectrogram", "sddm_set_conv_tuning", "sddm_initial_state", "sddm_schedule", "sddm_profile_enable",
            "sddm_profile_read", "sddm_profile_ops")
 
@@ -52,6 +52,7 @@ def lib():
         L.sddm_sample_noise.argtypes = [vp, vp, i64, i64, vp, vp, vp]
         L.sddm_sample_continuous.argtypes = [vp, vp, i64, i64, u64, i64, vp, vp, c_int, vp]
         L.sddm_network_forward.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp]
+        L.sddm_dual_transformer.argtypes = [vp, vp, i64, i64, i64, vp, vp]
         L.sddm_transition.argtypes = [vp, c_int, vp, vp, vp, c_int, i64, i64, u64, i64, vp, vp]
         L.sddm_q_sample.argtypes = [vp, c_int, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp]
         L.sddm_log_spectrogram.argtypes = [vp, i64, i64, c_int, c_int, vp, vp, c_int, vp, vp]
@@ -180,6 +181,12 @@ class Context:
         B, N = x_t.shape[0], x_t.shape[-1]
         check(lib().sddm_network_forward(self._h, _ptr(cond), _ptr(x_t), _ptr(noise_level), B, N,
                                          _ptr(eps_out), _stream(torch, cond.device)))
+
+    def dual_transformer(self, x, out):
+        """sddm_dual_transformer: x, out [B, 160, dim2, dim1] fp32 on the device (UNetTST contexts)."""
+        import torch
+        B, _, dim2, dim1 = x.shape
+        check(lib().sddm_dual_transformer(self._h, _ptr(x), B, dim2, dim1, _ptr(out), _stream(torch, x.device)))
 
     def transition(self, mode, x_t, eps, cond, t, out, seed, row_offset=0):
         import torch
