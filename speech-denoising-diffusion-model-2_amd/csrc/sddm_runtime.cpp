@@ -1,5 +1,5 @@
 // libsddm_hip runtime: context, parameter registry, weight packer (WeightPacker) and the C ABI
-// declared in include/sddm_hip.h, over six network paths:
+// declared in include/sddm_hip.h, over seven network paths:
 //   UNetModified2        this file: the per-batch plan of one reverse step, run in lanes whose step
 //                        graphs replay concurrently (build_plan, sample_impl); UNetTST is the same
 //                        plan with the Dual_Transformer op (dual_transformer.h) in place of mid.0
@@ -7,7 +7,8 @@
 //   WaveGrad, DenoiseWaveGrad1 / 3  wg_runtime.h   >  sequential networks: each implements SeqNet, and
 //   Waveunet3            wu_runtime.h  |   seq_sample / seq_forward here drive whichever is configured
 //   Waveunet2            wu2_runtime.h |
-//   Waveunet             wu1_runtime.h /
+//   Waveunet             wu1_runtime.h |
+//   CAUNet               cau_runtime.h /
 // A further sequential network is one such header and one branch on net_type in sddm_configure.
 //
 // Reference counterparts:
@@ -295,7 +296,8 @@ struct sddm_ctx;
 struct WeightPacker;
 
 // A sequential network: its forward is one launch sequence on the caller's stream.  DiffWave
-// (dw_runtime.h), the WaveGrad family (wg_runtime.h), Waveunet3 (wu_runtime.h), Waveunet2 (wu2_runtime.h) and Waveunet (wu1_runtime.h) derive from it;
+// (dw_runtime.h), the WaveGrad family (wg_runtime.h), Waveunet3 (wu_runtime.h), Waveunet2 (wu2_runtime.h), Waveunet (wu1_runtime.h)
+// and CAUNet (cau_runtime.h) derive from it;
 // seq_sample / seq_forward below drive any of them.  UNetModified2 runs in lanes and graphs instead
 struct SeqNet {
   std::map<std::string, std::vector<int64_t>> shapes;  // state-dict shapes (set by sddm_configure)
@@ -659,6 +661,7 @@ static int seq_forward(sddm_ctx* c, const float* cond, const float* x_t, const f
 #include "wu_runtime.h"
 #include "wu2_runtime.h"
 #include "wu1_runtime.h"
+#include "cau_runtime.h"
 
 // ---------------------------------------------------------------------------------------------
 // plan: the launch sequence of one UNetModified2 step for batch B
@@ -1547,6 +1550,14 @@ int sddm_configure(sddm_ctx* c, const char* json) {
     const auto shapes = wu1_param_shapes(us->net);
     return finish_configure(c, T, tabs, shapes, std::move(us), -1);
   }
+  if (c->net_type == "CAUNet") {                                 // CAUNet.py:307-374, config_caunet.json
+    if (c->arch_type != "SDDM") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "CAUNet needs arch SDDM (its condition is a waveform)");
+    auto us = std::make_unique<CAUState>();
+    const int r = cau_check_config(net.at("args"), *us);
+    if (r) return r;
+    const auto shapes = cau_param_shapes(*us);
+    return finish_configure(c, T, tabs, shapes, std::move(us), -1);
+  }
   // UNetTST (UNetTST.py:270-392): UNetModified2 with mid = Dual_Transformer and no final Swish in the noise MLP
   const bool tst = c->net_type == "UNetTST";
   if (c->net_type != "UNetModified2" && !tst) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "network type '%s'", c->net_type.c_str());
@@ -1823,15 +1834,19 @@ int sddm_network_forward(sddm_ctx* c, const float* cond, const float* x_t, const
   return SDDM_OK;
 }
 
-// The Dual_Transformer of a UNetTST context alone (UNetTST.py:212-233).  Only the mid.* parameters
-// need to be loaded: parameters outside mid that are still missing are packed as zeros
+// The Dual_Transformer of a UNetTST or CAUNet context alone (UNetTST.py:212-233, CAUNet.py:180-201).
+// Only the mid.* parameters need to be loaded: parameters outside mid that are still missing are
+// packed as zeros
 int sddm_dual_transformer(sddm_ctx* c, const float* in, int64_t B, int64_t dim2, int64_t dim1, float* out, void* stream) {
   if (!c || !c->configured) FAIL(SDDM_ERR_STATE, "context not configured");
-  if (c->net_type != "UNetTST") FAIL(SDDM_ERR_STATE, "sddm_dual_transformer needs a context configured for UNetTST");
+  const bool cau = c->net_type == "CAUNet";
+  if (c->net_type != "UNetTST" && !cau) FAIL(SDDM_ERR_STATE, "sddm_dual_transformer needs a context configured for UNetTST or CAUNet");
   if (!in || !out) FAIL(SDDM_ERR_INVALID_ARG, "NULL tensor");
   if (B < 1 || B > 65535 || dim2 < 1 || dim1 < 1) FAIL(SDDM_ERR_INVALID_ARG, "shape B=%lld dim2=%lld dim1=%lld", (long long)B, (long long)dim2, (long long)dim1);
-  if (dim2 * dim1 > kTstMaxTokens)
+  if (!cau && dim2 * dim1 > kTstMaxTokens)
     FAIL(SDDM_ERR_NOT_IMPLEMENTED, "dim2 * dim1 = %lld tokens: the Dual_Transformer kernel holds %d", (long long)(dim2 * dim1), kTstMaxTokens);
+  if (cau && (dim2 > (1 << 20) || dim1 > (1 << 20) || B * dim2 * dim1 > ((int64_t)1 << 24)))
+    FAIL(SDDM_ERR_SHAPE, "B * dim2 * dim1 = %lld tokens: the Dual_Transformer kernels index 2^24", (long long)(B * dim2 * dim1));
   SDDM_HIP_CHECK(hipSetDevice(c->device));
   for (auto& kv : c->params) {
     if (kv.second.loaded) continue;
@@ -1840,20 +1855,28 @@ int sddm_dual_transformer(sddm_ctx* c, const float* in, int64_t B, int64_t dim2,
     for (int64_t d : kv.second.shape) n *= d;
     if ((int64_t)kv.second.data.size() != n) kv.second.data.assign((size_t)n, 0.f);
   }
-  if (c->params_dirty) TRY(upload_weights(c));
+  if (c->params_dirty) TRY(cau ? seq_upload_weights(c) : upload_weights(c));
   if (c->tables_dirty) TRY(upload_tables(c));
   hipStream_t s = (hipStream_t)stream;
-  const int P = (int)(dim2 * dim1);
-  const size_t bytes = (size_t)B * P * kTstC * dtype_size(c->dtype);
+  const int P = (int)(dim2 * dim1), C = cau ? kCauC : kTstC;
+  const size_t bytes = ((size_t)B * P * C * dtype_size(c->dtype) + 255) & ~(size_t)255;
+  const size_t ws = cau ? cau_dt_ws_bytes(c->dtype, B, P) : 0;
   char* buf = nullptr;
-  SDDM_HIP_CHECK(hipMalloc(&buf, 2 * bytes));
-  DualTransformerArgs a{};
-  a.x = buf; a.out = buf + bytes; a.stats = nullptr;
-  a.wmat = c->warena.base + c->woff.at("mid.wmat"); a.wvec = c->warena.at<float>(c->woff.at("mid.wvec"));
-  a.dim2 = (int)dim2; a.dim1 = (int)dim1; a.n_tstb = c->ucfg.n_tstb;
-  hipError_t e = launch_dt_pack(c->dtype, in, buf, (int)B, kTstC, P, s);
-  if (e == hipSuccess) e = launch_dual_transformer(c->dtype, a, (int)B, s);
-  if (e == hipSuccess) e = launch_dt_unpack(c->dtype, buf + bytes, out, (int)B, kTstC, P, s);
+  SDDM_HIP_CHECK(hipMalloc(&buf, 2 * bytes + ws));
+  hipError_t e = launch_dt_pack(c->dtype, in, buf, (int)B, C, P, s);
+  if (cau) {
+    const CAUState& n = static_cast<const CAUState&>(*c->seq);
+    CauDtArgs a{buf, buf + bytes, c->warena.base + n.woff.at("mid.wmat"), c->warena.at<float>(n.woff.at("mid.wvec")), buf + 2 * bytes,
+                (int)B, (int)dim2, (int)dim1, n.n_tstb};
+    if (e == hipSuccess) e = launch_cau_dual_transformer(c->dtype, a, s);
+  } else {
+    DualTransformerArgs a{};
+    a.x = buf; a.out = buf + bytes; a.stats = nullptr;
+    a.wmat = c->warena.base + c->woff.at("mid.wmat"); a.wvec = c->warena.at<float>(c->woff.at("mid.wvec"));
+    a.dim2 = (int)dim2; a.dim1 = (int)dim1; a.n_tstb = c->ucfg.n_tstb;
+    if (e == hipSuccess) e = launch_dual_transformer(c->dtype, a, (int)B, s);
+  }
+  if (e == hipSuccess) e = launch_dt_unpack(c->dtype, buf + bytes, out, (int)B, C, P, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   (void)hipFree(buf);
   if (e != hipSuccess) FAIL(SDDM_ERR_HIP, "dual_transformer: %s", hipGetErrorString(e));

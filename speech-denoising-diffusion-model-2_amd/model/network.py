@@ -8,7 +8,11 @@ the same convolution with the output channels split over the grid) and Waveunet3
 config_waveunet2.json, config_waveunet.json and config_waveunet3.json.  UNetTST (config_unettst.json) is
 UNetModified2 with the dual-path transformer block Dual_Transformer (multi-head attention and a
 bidirectional GRU along the rows, then along the columns of the bottom level) in place of ``mid``; the
-block is also a module of its own.  The reference's CAUNet, TSTNN and SNR-estimator networks are not built."""
+block is also a module of its own.  CAUNet (config_caunet.json) is a causal dense-block U-Net over the
+frames (dilated (2,3) convs with LayerNorm over the frame and PReLU, a strided downsample and a sub-pixel
+upsample) around the same block at d_model 32 (``model.CAUNet.Dual_Transformer``: per-channel PReLUs, any
+number of frames).  The reference's TSTNN and SNR-estimator networks are not built."""
+from .CAUNet import CAUNet  # noqa: F401
 from .UNetModified2 import UNetModified2  # noqa: F401
 from .UNetTST import Dual_Transformer, UNetTST  # noqa: F401
 from .diffwave import DiffWave  # noqa: F401

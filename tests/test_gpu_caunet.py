@@ -1,0 +1,398 @@
+"""GPU: CAUNet (reference model/CAUNet.py:307-374, config_caunet.json) and its Dual_Transformer at
+d_model 32 (CAUNet.py:152-201) under SDDM.infer (model.py:50-124) through the facade and libsddm_hip,
+against goldens generated from the reference and the torch oracle pinned by test_caunet.py.
+
+The test that pins the block's wiring is test_dual_transformer_matches_reference: float32, the block
+alone, relative rms <= 2e-5.  Swapping the r / z gates of the last column GRU moves the block's output
+by 1.3e-4 ... 2.8e-4 relative at dim2 >= 2 (test_caunet.py prints it) and the whole network's by
+4.6e-5 at N = 704, which the float32 network bar (1e-4 x max(1, rms)) does not see.
+
+16-bit bars (_bar16, as test_gpu_unettst.py): the project's 3e-2 (bfloat16) / 5e-3 (float16) where
+the CPU emulation (the oracle's `rounding`: what the kernels round) is at most half of it, else twice
+the emulation.  Every test prints its emulation and its measurement.  CPU emulation, relative rms
+against the float64 oracle:
+  Dual_Transformer (2,8) / (17,8) / (70,8)   bfloat16 3.73e-3 / 3.63e-3 / 3.71e-3   float16 4.59e-4 / 4.51e-4 / 4.61e-4
+  forward B=2, N=704 / 16448                 bfloat16 1.01e-2 / 8.99e-3             float16 1.29e-3 / 1.12e-3
+so every bar is the project's.  Measured on MI355X (rms of the difference / rms of the reference
+unless noted):
+  Dual_Transformer vs golden, float32, six shapes    2.6e-7 ... 2.8e-7   (bar 2e-5); vs oracle at (256,8) 2.2e-7
+  Dual_Transformer vs oracle (2,8) / (17,8) / (70,8)  bfloat16 3.73e-3 / 3.62e-3 / 3.70e-3   float16 4.51e-4 / 4.51e-4 / 4.60e-4
+  Dual_Transformer(64, 64, 0, 2) alone, 5x8, B=3     1.9e-7
+  forward vs golden, B=2, N=704, float32             1.65e-6 rms (use_affine_level true: 1.65e-6)
+  forward vs oracle, float32, N=128 ... 16448        1.1e-6 ... 1.8e-6 rms;   n_TSTB=1: 1.4e-6 rms
+  forward vs oracle, B=2, N=704 / 16448              bfloat16 9.52e-3 / 9.02e-3   float16 1.27e-3 / 1.12e-3
+  sampling vs golden, every x_t, six cases           <= 6.5e-7 rms
+  SDDM.forward vs oracle                             1.9e-6 rms
+  rows, row shards, two ranks                        bit-equal
+"""
+import functools
+import json
+import os
+import struct
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.multiprocessing as mp
+
+import _caunet_oracle as O
+from _helpers import golden, rms
+from _weights import make_params
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SCHED = ("linear", 3, 1e-4, 0.05)
+MODES = ("original", "condition_in", "sr3", "supportive", "conditional")
+DT_DIM2 = (1, 2, 3, 10, 17, 70)
+DTYPES = ("float32", "bfloat16", "float16")
+_NETS = {}
+
+
+def _args(**change):
+    return dict(O.ARGS, **change)
+
+
+@functools.lru_cache(maxsize=None)
+def _params(n_tstb=6, affine=False):
+    return make_params(O.param_shapes(_args(n_TSTB=n_tstb, use_affine_level=affine)), 0)
+
+
+def _net(N, dtype="float32", n_tstb=6, affine=False):
+    """One facade network per (length, dtype, variant), shared by the tests (its weights never change)."""
+    key = (N, dtype, n_tstb, affine)
+    if key not in _NETS:
+        import model.network as NW
+        n = NW.CAUNet(num_samples=N, **_args(n_TSTB=n_tstb, use_affine_level=affine))
+        n.load_state_dict({k: torch.from_numpy(v) for k, v in _params(n_tstb, affine).items()})
+        n.compute_dtype = dtype
+        n.mid.compute_dtype = dtype
+        _NETS[key] = n.cuda()
+    return _NETS[key]
+
+
+def _model(N, mode="original", noise_condition="sqrt_alpha_bar", dtype="float32"):
+    import model.diffusion as D
+    import model.model as M
+    d = D.GaussianDiffusion(*SCHED, device="cuda")
+    return M.SDDM(d, _net(N, dtype), noise_condition=noise_condition, p_transition=mode, compute_dtype=dtype).cuda()
+
+
+def _inputs(B, N, seed):
+    rng = np.random.default_rng(seed)
+    cond = np.clip(0.3 * rng.standard_normal((B, 1, N)), -1, 1).astype(np.float32)
+    x_t = rng.standard_normal((B, 1, N)).astype(np.float32)
+    nl = rng.uniform(0.05, 0.99, B).astype(np.float32)
+    return cond, x_t, nl
+
+
+def _gate(ref):
+    return max(1.0, rms(ref, 0))
+
+
+def _bar16(dtype, emu):
+    """The 16-bit bar: the project's where the CPU emulation's error is at most half of it, else twice
+    the emulation's."""
+    project = {"bfloat16": 3e-2, "float16": 5e-3}[dtype]
+    return project if emu <= 0.5 * project else 2.0 * emu
+
+
+def _run(net, cond, x_t, nl):
+    return net(torch.from_numpy(cond).cuda(), torch.from_numpy(x_t).cuda(), torch.from_numpy(nl).cuda()).cpu().numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_case(B, N, n_tstb=6):
+    cond, x_t, nl = _inputs(B, N, seed=31)
+    return cond, x_t, nl, O.forward(_params(n_tstb), cond, x_t, nl, args=_args(n_TSTB=n_tstb))
+
+
+@functools.lru_cache(maxsize=None)
+def _block_256():
+    """The block's input at the config's length ([2, 64, 256, 8]; not stored as a golden) and the oracle's output."""
+    x = np.random.default_rng(41).standard_normal((2, 64, 256, 8)).astype(np.float32)
+    return x, O.dual_transformer(_params(), x)
+
+
+# ---- 7, 8, 9: the block alone
+@pytest.mark.parametrize("dim2", DT_DIM2)
+def test_dual_transformer_matches_reference(torch_cuda, dim2):
+    z = golden("caunet.npz")
+    x, ref = z[f"dt/{dim2}x8/x"], z[f"dt/{dim2}x8/y"]
+    y = _net(704).mid(torch.from_numpy(x).cuda()).cpu().numpy()
+    assert y.shape == ref.shape
+    rel = rms(y, ref) / rms(ref, 0)
+    print(f"Dual_Transformer {dim2}x8 float32: relative rms vs reference {rel:.3e}")
+    assert np.isfinite(y).all() and rel <= 2e-5
+
+
+def test_dual_transformer_matches_oracle_at_256_frames(torch_cuda):
+    x, ref = _block_256()
+    y = _net(704).mid(torch.from_numpy(x).cuda()).cpu().numpy()
+    rel = rms(y, ref) / rms(ref, 0)
+    print(f"Dual_Transformer 256x8 float32: relative rms vs oracle {rel:.3e}")
+    assert np.isfinite(y).all() and rel <= 2e-5
+
+
+@pytest.mark.parametrize("dim2", [2, 17, 70])
+@pytest.mark.parametrize("dtype", ["bfloat16", "float16"])
+def test_dual_transformer_16bit_matches_oracle(torch_cuda, dtype, dim2):
+    z = golden("caunet.npz")
+    x = z[f"dt/{dim2}x8/x"]
+    ref = O.dual_transformer(_params(), x)
+    emu = rms(O.dual_transformer(_params(), x, rounding=getattr(torch, dtype)), ref) / rms(ref, 0)
+    y = _net(704, dtype).mid(torch.from_numpy(x).cuda()).cpu().numpy()
+    rel = rms(y, ref) / rms(ref, 0)
+    print(f"Dual_Transformer {dim2}x8 {dtype}: relative rms vs oracle {rel:.3e} (CPU emulation {emu:.3e}, bar {_bar16(dtype, emu):.3e})")
+    assert np.isfinite(y).all() and rel <= _bar16(dtype, emu)
+
+
+def test_dual_transformer_alone_as_a_module(torch_cuda):
+    """A stand-alone Dual_Transformer(64, 64, 0, 2) (its own context; only mid.* is loaded)."""
+    from model.CAUNet import Dual_Transformer
+    shapes = {k[4:]: s for k, s in O.dual_transformer_shapes(64, 2).items()}
+    P = make_params(shapes, 3)
+    m = Dual_Transformer(64, 64, 0, 2)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in P.items()})
+    x = np.random.default_rng(5).standard_normal((3, 64, 5, 8)).astype(np.float32)
+    ref = O.dual_transformer(P, x, n_tstb=2, prefix="")
+    y = m.cuda()(torch.from_numpy(x).cuda()).cpu().numpy()
+    rel = rms(y, ref) / rms(ref, 0)
+    print(f"Dual_Transformer(64, 64, 0, 2) alone, 5x8, B=3: relative rms vs oracle {rel:.3e}")
+    assert rel <= 2e-5
+
+
+# ---- 10, 11: the whole forward
+@pytest.mark.parametrize("affine", [False, True])
+def test_forward_matches_reference(torch_cuda, affine):
+    z = golden("caunet.npz")
+    ref = z["fwa/eps" if affine else "fw/eps"]
+    eps = _run(_net(704, affine=affine), z["fw/cond"], z["fw/x_t"], z["fw/noise_level"])
+    assert eps.shape == ref.shape and np.isfinite(eps).all()
+    err = rms(eps, ref)
+    print(f"CAUNet float32 use_affine_level={affine} B=2 N=704: rms vs reference {err:.3e} (ref rms {rms(ref, 0):.3f})")
+    assert err <= 1e-4 * _gate(ref)
+
+
+@pytest.mark.parametrize("B,N", [(3, 128), (3, 320), (3, 1152), (2, 4544), (2, 16448)])
+def test_forward_matches_oracle(torch_cuda, B, N):
+    """One frame (every causal tap reads padding), 4 frames (dilation 4 reads padding only), 17 and 70
+    frames (rows of several batch items in one conv block) and the config's 256."""
+    cond, x_t, nl, ref = _oracle_case(B, N)
+    eps = _run(_net(N), cond, x_t, nl)
+    err = rms(eps, ref)
+    print(f"CAUNet float32 B={B} N={N}: rms vs oracle {err:.3e} (ref rms {rms(ref, 0):.3f})")
+    assert eps.shape == (B, 1, N) and np.isfinite(eps).all() and err <= 1e-4 * _gate(ref)
+
+
+def test_one_transformer_block_matches_oracle(torch_cuda):
+    cond, x_t, nl, ref = _oracle_case(2, 704, 1)
+    eps = _run(_net(704, n_tstb=1), cond, x_t, nl)
+    err = rms(eps, ref)
+    print(f"CAUNet n_TSTB=1 B=2 N=704: rms vs oracle {err:.3e}")
+    assert err <= 1e-4 * _gate(ref)
+
+
+@pytest.mark.parametrize("N", [704, 16448])
+@pytest.mark.parametrize("dtype", ["bfloat16", "float16"])
+def test_forward_16bit_matches_oracle(torch_cuda, dtype, N):
+    cond, x_t, nl, ref = _oracle_case(2, N)
+    eps = _run(_net(N, dtype), cond, x_t, nl)
+    rel = rms(eps, ref) / rms(ref, 0)
+    emu = rms(O.forward(_params(), cond, x_t, nl, rounding=getattr(torch, dtype)), ref) / rms(ref, 0)
+    print(f"CAUNet {dtype} B=2 N={N}: relative rms vs oracle {rel:.3e} (CPU emulation {emu:.3e}, bar {_bar16(dtype, emu):.3e})")
+    assert np.isfinite(eps).all() and rel <= _bar16(dtype, emu)
+
+
+# ---- 12: rows are bit-identical
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_rows_are_independent_of_the_batch(torch_cuda, dtype):
+    net = _net(704, dtype)
+    cond, x_t, nl = (torch.from_numpy(a).cuda() for a in _inputs(3, 704, seed=2))
+    full = net(cond, x_t, nl)
+    assert torch.isfinite(full).all() and float(full.abs().max()) > 0
+    x = torch.from_numpy(np.random.default_rng(9).standard_normal((3, 64, 10, 8)).astype(np.float32)).cuda()
+    blk = net.mid(x)
+    assert torch.isfinite(blk).all() and float(blk.abs().max()) > 0
+    two = net(cond[:2].contiguous(), x_t[:2].contiguous(), nl[:2].contiguous())
+    assert torch.equal(two, full[:2])
+    for b in (0, 2):                                             # B = 1 is row 0 of B = 2 and row 2 of B = 3
+        one = net(cond[b:b + 1].contiguous(), x_t[b:b + 1].contiguous(), nl[b:b + 1].contiguous())
+        assert torch.equal(full[b:b + 1], one), b
+        assert torch.equal(blk[b:b + 1], net.mid(x[b:b + 1].contiguous())), b
+    assert torch.equal(blk[:2], net.mid(x[:2].contiguous()))
+
+
+# ---- 13: sampling
+@pytest.mark.parametrize("nc,mode", [("sqrt_alpha_bar", m) for m in MODES] + [("time_step", "original")])
+def test_sampling_matches_reference(torch_cuda, nc, mode):
+    """The reference's unmodified SDDM.infer: the output and every intermediate x_t; a second run is
+    bit-equal."""
+    z = golden("caunet.npz")
+    steps = z[f"inf/{nc}/{mode}/steps"]
+    cond = torch.from_numpy(z["inf/cond"]).cuda()
+    m = _model(704, mode, nc)
+    out = m.infer(cond, seed=7).cpu().numpy()
+    assert out.shape == steps[-1].shape
+    T = SCHED[1]
+    record = torch.empty((T,) + tuple(cond.shape), dtype=torch.float32, device="cuda")
+    out2 = torch.empty_like(cond)
+    m._context(cond.device).sample_continuous(cond, out2, record, 1, 7, 0)
+    errs = [rms(record[i].cpu().numpy(), steps[i]) for i in range(T)]
+    print(f"CAUNet {nc} {mode}: rms of x_t per step {['%.2e' % e for e in errs]}")
+    for e, s in zip(errs, steps):
+        assert e <= 1e-4 * _gate(s)
+    assert torch.equal(out2.cpu(), torch.from_numpy(out))
+
+
+def test_row_sharding_is_bit_identical(torch_cuda):
+    """Rows sampled in two shards (row_offset) equal the rows of one batch; sharded_infer without a
+    process group is model.infer."""
+    import model.model as M
+    m = _model(704, "conditional", dtype="bfloat16")
+    cond = torch.from_numpy(_inputs(4, 704, seed=1)[0]).cuda()
+    full = m.infer(cond, seed=11)
+    a = m.infer(cond[:2].contiguous(), seed=11, row_offset=0)
+    b = m.infer(cond[2:].contiguous(), seed=11, row_offset=2)
+    assert torch.isfinite(full).all() and float(full.abs().max()) > 0
+    assert torch.equal(full, torch.cat([a, b]))
+    assert torch.equal(M.sharded_infer(m, cond, seed=11), full)
+
+
+def _paths():
+    sys.path.insert(0, os.path.dirname(HERE))
+    sys.path.insert(0, HERE)
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "speech-denoising-diffusion-model-2_amd"))
+
+
+def _shard_model():
+    import model.diffusion as D
+    import model.model as M
+    import model.network as NW
+    dev = torch.device("cuda", 0)
+    net = NW.CAUNet(num_samples=704, **O.ARGS)
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in make_params(O.param_shapes(), 0).items()})
+    net.compute_dtype = "bfloat16"
+    m = M.SDDM(D.GaussianDiffusion("linear", 3, 1e-4, 0.05, device=dev), net, p_transition="sr3", compute_dtype="bfloat16")
+    return m.to(dev)
+
+
+def _shard_cond():
+    from sddm_hip.synth import noisy_speech
+    return torch.from_numpy(noisy_speech(3, 704, seed=977)).cuda()
+
+
+def _rank(rank, world, port, out_path):
+    _paths()
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from model.model import sharded_infer
+    out = sharded_infer(_shard_model(), _shard_cond(), seed=13)
+    if rank == 0:
+        np.save(out_path, out.cpu().numpy())
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_two_ranks_equal_single_run(torch_cuda, tmp_path):
+    """sharded_infer in two spawned ranks that share cuda:0 and gather over gloo; an odd batch, so the
+    last rank's shard is padded."""
+    import socket
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    sharded = str(tmp_path / "sharded.npy")
+    mp.spawn(_rank, args=(2, port, sharded), nprocs=2, join=True)
+    a = np.load(sharded)
+    b = _shard_model().infer(_shard_cond(), seed=13).cpu().numpy()
+    assert a.shape == (3, 1, 704) and np.isfinite(a).all() and float(np.abs(a).max()) > 0
+    assert np.array_equal(a, b)
+
+
+# ---- 14: SDDM.forward, configure-time refusals, infer.py
+def test_sddm_forward_matches_oracle(torch_cuda):
+    """SDDM.forward (evaluation only): q-sample at fixed t, then the network."""
+    B, N = 2, 704
+    rng = np.random.default_rng(23)
+    target = torch.from_numpy(rng.uniform(-0.5, 0.5, (B, 1, N)).astype(np.float32)).cuda()
+    cond = (target + torch.from_numpy(rng.uniform(-0.1, 0.1, (B, 1, N)).astype(np.float32)).cuda())
+    noise = torch.from_numpy(rng.standard_normal((B, 1, N)).astype(np.float32)).cuda()
+    m = _model(N)
+    with torch.no_grad():
+        predicted, got_noise = m(target, cond, noise=noise, t=torch.tensor([3, 1]), random_step=torch.tensor([0.25, 0.75]))
+    assert torch.equal(got_noise, noise) and tuple(predicted.shape) == (B, 1, N)
+    x_t, level, _ = m.diffusion.q_stochastic(target, noise, t=torch.tensor([3, 1]), random_step=torch.tensor([0.25, 0.75]))
+    ref = O.forward(_params(), cond.cpu().numpy(), x_t.cpu().numpy(), level.cpu().numpy())
+    err = rms(predicted.cpu().numpy(), ref)
+    print(f"CAUNet SDDM.forward: rms vs oracle {err:.3e}")
+    assert err <= 1e-4 * _gate(ref)
+
+
+def _cfg(**change):
+    return {"arch": {"type": "SDDM", "args": {}},
+            "diffusion": {"type": "GaussianDiffusion", "args": {"schedule": "linear", "n_timestep": 3}},
+            "network": {"type": "CAUNet", "args": _args(**change)}, "num_samples": 704}
+
+
+@pytest.mark.parametrize("name,value", [("inner_channel", 32), ("n_encode_layers", 3), ("dense_depth", 5), ("segment_len", 256),
+                                        ("segment_stride", 32), ("n_TSTB", 0)])
+def test_unsupported_arguments_are_refused_at_configure(torch_cuda, name, value):
+    import sddm_hip
+    with pytest.raises(NotImplementedError, match=name):
+        sddm_hip.Context(_cfg(**{name: value}), 0)
+
+
+def test_context_registers_the_reference_keys(torch_cuda):
+    import sddm_hip
+    ctx = sddm_hip.Context(_cfg(), 0)
+    assert ctx.missing() == 450
+    ctx.close()
+
+
+def _write_pcm16(path, x, sr=16000):
+    pcm = np.clip(np.round(x * 32768), -32768, 32767).astype("<i2").tobytes()
+    hdr = struct.pack("<4sI4s4sIHHIIHH4sI", b"RIFF", 36 + len(pcm), b"WAVE", b"fmt ", 16, 1, 1, sr, 2 * sr, 2, 16,
+                      b"data", len(pcm))
+    with open(path, "wb") as f:
+        f.write(hdr + pcm)
+
+
+def test_infer_cli_end_to_end(torch_cuda, tmp_path):
+    """infer.py with configs/config_caunet.json at chunks of 704 samples and T = 3: WAV in, chunk,
+    denoise, stitch, WAV out."""
+    import infer
+    import model.diffusion as D
+    import model.model as M
+    from data_loader import wav_io
+    from parse_config import ConfigParser, read_json
+    N = 704
+    rng = np.random.default_rng(4)
+    for d in ("clean", "noisy"):
+        os.makedirs(tmp_path / "data" / d)
+    lengths = [1800, 500]
+    for i, n in enumerate(lengths):
+        c = 0.3 * np.sin(np.arange(n) * 0.05)
+        _write_pcm16(tmp_path / "data" / "clean" / f"u{i}.wav", c)
+        _write_pcm16(tmp_path / "data" / "noisy" / f"u{i}.wav", c + rng.uniform(-0.05, 0.05, n))
+    cfg = read_json(os.path.join(os.path.dirname(infer.__file__), "configs", "config_caunet.json"))
+    assert cfg["network"]["type"] == "CAUNet" and cfg["num_samples"] == 16448
+    cfg["num_samples"] = N
+    cfg["diffusion"]["args"].update({"n_timestep": 3, "linear_end": 0.05})
+    cfg["infer_dataset"]["args"]["data_root"] = str(tmp_path / "data")
+    cfg["infer_data_loader"]["args"].update({"batch_size": 1, "num_workers": 0})
+    cfg["trainer"]["save_dir"] = str(tmp_path / "runs")
+    ref_model = M.SDDM(D.GaussianDiffusion("linear", 3, 1e-4, 0.05, device="cpu"), _net(N))
+    ck = tmp_path / "model_best.pth"
+    torch.save({"arch": "SDDM", "epoch": 1,
+                "state_dict": {"module." + k: v.cpu() for k, v in ref_model.state_dict().items()},
+                "config": json.loads(json.dumps(cfg))}, ck)
+    config = ConfigParser(cfg, resume=ck, run_id="e2e")
+    log = infer.main(config, seed=100)
+    assert np.isfinite(log["loss"])
+    for i, n in enumerate(lengths):
+        out, sr = wav_io.load(os.path.join(str(config.save_dir), "samples", "output", f"u{i}.wav"))
+        assert sr == 16000 and out.shape[1] % N == 0 and out.shape[1] >= n
+        assert torch.isfinite(out).all() and float(out.abs().max()) > 0
