@@ -1,13 +1,12 @@
 // libsddm_hip runtime: context, parameter registry, weight packer (WeightPacker) and the C ABI
-// declared in include/sddm_hip.h, over seven network paths:
+// declared in include/sddm_hip.h, over these network paths:
 //   UNetModified2        this file: the per-batch plan of one reverse step, run in lanes whose step
 //                        graphs replay concurrently (build_plan, sample_impl); UNetTST is the same
 //                        plan with the Dual_Transformer op (dual_transformer.h) in place of mid.0
 //   DiffWave             dw_runtime.h  \
 //   WaveGrad, DenoiseWaveGrad1 / 3  wg_runtime.h   >  sequential networks: each implements SeqNet, and
 //   Waveunet3            wu_runtime.h  |   seq_sample / seq_forward here drive whichever is configured
-//   Waveunet2            wu2_runtime.h |
-//   Waveunet             wu1_runtime.h |
+//   Waveunet2, Waveunet  wu2_runtime.h |
 //   CAUNet               cau_runtime.h /
 // A further sequential network is one such header and one branch on net_type in sddm_configure.
 //
@@ -296,8 +295,8 @@ struct sddm_ctx;
 struct WeightPacker;
 
 // A sequential network: its forward is one launch sequence on the caller's stream.  DiffWave
-// (dw_runtime.h), the WaveGrad family (wg_runtime.h), Waveunet3 (wu_runtime.h), Waveunet2 (wu2_runtime.h), Waveunet (wu1_runtime.h)
-// and CAUNet (cau_runtime.h) derive from it;
+// (dw_runtime.h), the WaveGrad family (wg_runtime.h), Waveunet3 (wu_runtime.h), Waveunet2 and Waveunet
+// (wu2_runtime.h) and CAUNet (cau_runtime.h) derive from it;
 // seq_sample / seq_forward below drive any of them.  UNetModified2 runs in lanes and graphs instead
 struct SeqNet {
   std::map<std::string, std::vector<int64_t>> shapes;  // state-dict shapes (set by sddm_configure)
@@ -660,7 +659,6 @@ static int seq_forward(sddm_ctx* c, const float* cond, const float* x_t, const f
 #include "wg_runtime.h"
 #include "wu_runtime.h"
 #include "wu2_runtime.h"
-#include "wu1_runtime.h"
 #include "cau_runtime.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -1532,22 +1530,12 @@ int sddm_configure(sddm_ctx* c, const char* json) {
     const auto shapes = wu_param_shapes(us->net);
     return finish_configure(c, T, tabs, shapes, std::move(us), -1);
   }
-  if (c->net_type == "Waveunet2") {                              // waveunet2.py:226-324, config_waveunet2.json
-    if (c->arch_type != "SDDM") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "Waveunet2 needs arch SDDM (its condition is a waveform)");
-    const int r = wu2_check_config(net.at("args"));
+  if (const wu2::Net* wn = wu2::find_net(c->net_type)) {         // waveunet2.py:226-324, waveunet.py:358-506
+    if (c->arch_type != "SDDM") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "%s needs arch SDDM (its condition is a waveform)", wn->name);
+    const int r = wn->check_config(net.at("args"));
     if (r) return r;
-    auto us = std::make_unique<WU2State>();
-    const auto shapes = wu2_param_shapes(us->net);
-    return finish_configure(c, T, tabs, shapes, std::move(us), -1);
-  }
-  if (c->net_type == "Waveunet") {                               // waveunet.py:358-506, config_waveunet.json
-    if (c->arch_type != "SDDM") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "Waveunet needs arch SDDM (its condition is a waveform)");
-    const int r = wu1_check_config(net.at("args"));
-    if (r) return r;
-    auto us = std::make_unique<WU1State>();
-    auto set = [](const char* name) { const char* v = std::getenv(name); return v && v[0] && v[0] != '0'; };
-    us->fold = set("SDDM_WU_NO_FOLD") ? 0 : (set("SDDM_WU_FOLD_ALL") ? 2 : 1);
-    const auto shapes = wu1_param_shapes(us->net);
+    auto us = std::make_unique<WUFilmState>(*wn);
+    const auto shapes = wu2_param_shapes(*us);
     return finish_configure(c, T, tabs, shapes, std::move(us), -1);
   }
   if (c->net_type == "CAUNet") {                                 // CAUNet.py:307-374, config_caunet.json

@@ -1,6 +1,6 @@
 // Waveunet denoiser (reference model/waveunet.py:358-506 at the arguments of config_waveunet.json:
-// twelve levels, 24 ... 288 channels) for SDDM.infer (model.py:50-124).  wu1_runtime.h holds the
-// layer sequence.
+// twelve levels, 24 ... 288 channels) for SDDM.infer (model.py:50-124).  wu2_runtime.h holds the
+// layer sequence, which is Waveunet2's with another table.
 //
 // The layers are Waveunet2's (waveunet2.hip) with more channels: the convs are launches of
 // wu_conv_kernel (wu_conv_impl.h) under the policy Wu1Conv below, which is Waveunet2's input
@@ -11,7 +11,6 @@
 // (WU_DOWN4, NCO = 6, 16-bit; Waveunet2: 52.5 KB).  The 16-bit instantiations with five or more
 // fragments run two blocks per CU by registers, as Waveunet2's do, the smaller ones three or four.
 // Every group stages and transforms the input slab again.  The statistics partials [B][slots][C][2] are unchanged: the groups own disjoint channels.
-#include "wu1_kernels.h"
 #include "wu2_conv_policy.h"
 
 namespace sddm {
@@ -45,7 +44,7 @@ struct Wu1Conv : Wu2ConvBase<WU1ConvArgs, kWu1MaxC, true> {
 hipError_t launch_wu1_conv(int dtype, const WU2ConvArgs& a2, hipStream_t s) {
   WU1ConvArgs a{};
   static_cast<WU2ConvArgs&>(a) = a2;
-  const hipError_t e = wu1_conv_check(a);
+  const hipError_t e = wu2_conv_check(a, kWu1MaxC, kWu1MaxC, 2 * kWu1MaxC);
   if (e != hipSuccess) return e;
   a.gco = wu1_conv_group(a.mode, a.Cout);
   return wu_conv_dispatch<Wu1Conv>(dtype, a, s);

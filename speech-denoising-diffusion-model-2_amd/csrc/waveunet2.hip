@@ -53,15 +53,8 @@ struct Wu2Conv : Wu2ConvBase<WU2ConvArgs, 96, false> {
 };
 
 hipError_t launch_wu2_conv(int dtype, const WU2ConvArgs& a, hipStream_t s) {
-  if (a.mode < WU_CONV5 || a.mode > WU_UP4 || a.B < 1 || a.B > 65535 || a.Lin < 1 || a.Lout < 1) return hipErrorInvalidValue;
-  if (!a.src || !a.w || !a.bias || !a.out) return hipErrorInvalidValue;
-  if (a.Cin % 8 || a.Cin < 8 || a.Cin > 96 || a.Cout % 8 || a.Cout < 8 || a.Cout > 144) return hipErrorInvalidValue;
-  if (((a.mode == WU_CONV5 || a.mode == WU_CONV3) && a.Lout != a.Lin) || (a.mode == WU_DOWN4 && a.Lin != 2 * a.Lout) ||
-      (a.mode == WU_UP4 && a.Lout != 2 * a.Lin))
-    return hipErrorInvalidValue;
-  if ((a.scale == nullptr) != (a.shift == nullptr) || (a.film && (!a.scale || a.mode != WU_CONV5))) return hipErrorInvalidValue;
-  if (a.enc_dim && (a.enc_dim != a.Cout || a.enc_dim > 96 || a.enc_dim % 2)) return hipErrorInvalidValue;
-  if (a.enc_dim && !a.lv.levels && (!a.lv.t_dev || (!a.lv.time_step && !a.lv.table))) return hipErrorInvalidValue;
+  const hipError_t e = wu2_conv_check(a, 96, 144, 144);
+  if (e != hipSuccess) return e;
   return wu_conv_dispatch<Wu2Conv>(dtype, a, s);
 }
 

@@ -1,4 +1,4 @@
-// Host code the Waveunet3 and Waveunet2 paths of the runtime share (included by wu_runtime.h and
+// Host code the Waveunet3 and the FiLM Wave-U-Net paths of the runtime share (included by wu_runtime.h and
 // wu2_runtime.h, i.e. by sddm_runtime.cpp after sddm_ctx and SeqNet).
 #pragma once
 #include "wu_kernels.h"
@@ -15,10 +15,15 @@ static void wu_add_conv(sddm_ctx* c, WeightPacker& pk, const std::string& name, 
       }
 }
 
-// the (B, N) a network that halves the length three times takes; `net` names it in the message
-static int wu_check_shape(const char* net, int64_t B, int64_t N) {
+// the (B, N) a network that halves the length `halvings` (at most eleven) times takes; `net` names
+// it in the message
+static int wu_check_shape(const char* net, int64_t B, int64_t N, int halvings = 3) {
   if (B < 1 || B > 65535) FAIL(SDDM_ERR_INVALID_ARG, "batch %lld", (long long)B);
-  if (N < 8 || N % 8) FAIL(SDDM_ERR_SHAPE, "%lld samples is not a positive multiple of 8 (%s halves the length three times)", (long long)N, net);
+  static const char* const kTimes[] = {"zero", "one", "two", "three", "four", "five", "six", "seven", "eight", "nine", "ten", "eleven"};
+  const int hop = 1 << halvings;
+  if (N < hop || N % hop)
+    FAIL(SDDM_ERR_SHAPE, "%lld samples is not a positive multiple of %d (%s halves the length %s times)", (long long)N, hop, net,
+         kTimes[halvings]);
   if (N > (int64_t)1 << 30) FAIL(SDDM_ERR_SHAPE, "%lld samples: %s positions are 32-bit", (long long)N, net);
   return SDDM_OK;
 }

@@ -4,7 +4,7 @@ The module tree only holds the parameters under the reference's state-dict keys
 (``waveunet.downsampling_blocks.0.pre_shortcut_convs.0.filter.weight`` ...; the learned resampling
 convs are ``downconv.filter.*`` and ``upconv.filter.*`` directly); the forward runs in libsddm_hip
 (csrc/waveunet1.hip, the conv kernel of csrc/wu_conv_impl.h with the layer's output channels split
-over the grid, wu1_runtime.h).  Supported: the arguments of config_waveunet.json -- twelve levels of
+over the grid; the layer sequence is csrc/wu2_runtime.h, shared with Waveunet2).  Supported: the arguments of config_waveunet.json -- twelve levels of
 24, 48, ..., 288 channels, 5-tap convs, learned 4-tap stride-2 resampling (res 'learned'), conv_type
 'gn', depth 1, two inputs; everything else is refused by the library when the context is
 configured.  The chunk length is any positive multiple of 2048 (eleven stride-2 levels).  The output

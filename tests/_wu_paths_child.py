@@ -2,11 +2,8 @@
 
     python _wu_paths_child.py OUT.npz
 
-The library reads SDDM_WU_NO_FOLD and SDDM_WU_FOLD_ALL when a context is configured, so each path
-is one fresh interpreter with its knob in the environment: SDDM_WU_NO_FOLD=1 sends every layer
-through the per-row kernel (as the default does: it folds at no length), SDDM_WU_FOLD_ALL=1 every
-layer shorter than 128 positions through the batch-folded kernel.  The child runs the facade
-Waveunet with the test weights and writes one npz:
+A fresh interpreter, so the library, its code objects and every context are loaded and configured
+by these forwards alone.  The child runs the facade Waveunet with the test weights and writes one npz:
 
   fw/<dtype>        eps of one forward on the inputs of the golden (B = 2, N = 2048), three dtypes
   odd/float32       eps at B = 3, N = 6144 (lengths 96 ... 3), the inputs of odd_inputs()

@@ -1,5 +1,5 @@
-"""The output bits of the sequential networks (DiffWave, the WaveGrad family, Waveunet3, Waveunet2),
-pinned across changes of the host code that drives them and across kernel refactors that claim bit
+"""The output bits of the sequential networks (DiffWave, the WaveGrad family, Waveunet3, Waveunet2,
+Waveunet), pinned across changes of the host code that drives them and across kernel refactors that claim bit
 equality.
 
 None of their kernels uses an atomic and every path's own tests assert run-to-run bit equality, so
@@ -12,7 +12,9 @@ The digests are recorded on the GPU with the library of the commit before the ch
 never with the code under test (tools/record_store_digests.py --module test_gpu_seq_digests).  The
 first 60 were recorded before the paths were given one loop and one packer.  The Waveunet2,
 float16, tiles and bottom entries were recorded before the two Wave-U-Nets were given one conv
-kernel and one stem kernel; that recording reproduced the first 60.
+kernel and one stem kernel; that recording reproduced the first 60.  The Waveunet entries (the
+12-level network) were recorded before Waveunet2 and Waveunet were given one runtime and the
+batch-folded kernel of Waveunet's short levels was removed; that recording reproduced the first 112.
 
 Cases are <net>/<dtype>/<kind>, B = 2, N = two hops (296 for the Waveunets: the smallest sizes of
 the path tests at which every level has more than one position), T = 4, one library context per
@@ -31,6 +33,13 @@ forward-only kinds in all three dtypes, the shapes of their test_forward_matches
            128-position tiles and a partial last one, WU_UP4 blocks use both 64-position halves
   bottom   network_forward at B = 3, N = 8: the bottleneck is one position, the transposed conv
            starts from one position, every tile is partial
+The 12-level Waveunet takes multiples of 2048 only: its N is 2048 (the lengths are 2048 ... 1: every
+level below 128 positions, the one-position bottleneck and a transposed conv that starts from one
+position are in every run), its reshape length 4096.  It runs the five kinds in float32 and
+bfloat16, fw and sample under time_step and in float16, and one forward-only kind of its own in all
+three dtypes:
+  odd      network_forward at B = 3, N = 6144 (96 ... 3): no powers of two, partly filled tiles, an
+           odd batch
 """
 import functools
 import hashlib
@@ -42,6 +51,7 @@ import pytest
 
 import _denoise_wavegrad_oracle as DO
 import _waveunet2_oracle as W2O
+import _waveunet_oracle as W1O
 import _waveunet3_oracle as WO
 from _helpers import GOLDEN, diffwave_params, wavegrad_params
 from _weights import make_params
@@ -68,6 +78,16 @@ SHAPES = {"tiles": (2, 2072, 12), "bottom": (3, 8, 13)}   # kind -> rows, N, see
 CASES += [f"{n}/{d}/{k}" for n in WAVEUNETS[2:] for d in ("float32", "bfloat16") for k in KINDS]
 CASES += [f"{n}/float16/{k}" for n in WAVEUNETS for k in ("fw", "sample")]
 CASES += [f"{n}/{d}/{k}" for n in WAVEUNETS for d in ("float32", "bfloat16", "float16") for k in SHAPES]
+# the 12-level Waveunet, appended behind the first 112: its lengths are multiples of 2048
+NETS.update({"Waveunet": ("Waveunet", 2048, 4096, 0, 1, "sqrt_alpha_bar"),
+             "Waveunet-time_step": ("Waveunet", 2048, 4096, 0, 1, "time_step")})
+NET_ARGS["Waveunet"] = W1O.ARGS
+SHAPES12 = {"odd": (3, 6144, 14)}                         # kind -> rows, N, seed of the inputs
+ALL_SHAPES = {**SHAPES, **SHAPES12}
+CASES += [f"Waveunet/{d}/{k}" for d in ("float32", "bfloat16") for k in KINDS]
+CASES += [f"Waveunet-time_step/{d}/{k}" for d in ("float32", "bfloat16") for k in ("fw", "sample")]
+CASES += [f"Waveunet/float16/{k}" for k in ("fw", "sample")]
+CASES += [f"Waveunet/{d}/{k}" for d in ("float32", "bfloat16", "float16") for k in SHAPES12]
 
 _CTX = {}
 
@@ -82,6 +102,8 @@ def _params(net_type):
         return make_params(WO.param_shapes(), 0)
     if net_type == "Waveunet2":
         return make_params(W2O.param_shapes(), 0)
+    if net_type == "Waveunet":
+        return make_params(W1O.param_shapes(), 0)
     return make_params(DO.param_shapes(net_type), 0)
 
 
@@ -141,8 +163,8 @@ def run_case(torch, case):
     dev = torch.device("cuda", 0)
     if kind == "fw":
         return _forward(torch, ctx, net, B, N, 5)
-    if kind in SHAPES:
-        return _forward(torch, ctx, net, *SHAPES[kind])
+    if kind in ALL_SHAPES:
+        return _forward(torch, ctx, net, *ALL_SHAPES[kind])
     if kind == "reshape":
         first = _forward(torch, ctx, net, B, N, 5)
         other = _forward(torch, ctx, net, 3, N2, 6)

@@ -12,15 +12,15 @@ oracle's `rounding`) gives, relative rms against the reference,
 The bar is the project's (3e-2 / 5e-3) where the emulation is at most half of it, else twice the
 emulation (_bar16): 3e-2 / 5e-3 at the golden shape, 3.11e-2 / 5e-3 at N = 16384.
 Measured on MI355X (rms of the difference / rms of the reference unless noted):
-  forward vs golden                   float32 1.3e-6   bfloat16 1.25e-2   float16 1.76e-3 (both paths)
+  forward vs golden                   float32 1.3e-6   bfloat16 1.25e-2   float16 1.76e-3
   forward at B=2, N=16384 vs oracle   bfloat16 1.45e-2  float16 2.17e-3
-  folded vs per-row, 16-bit           bit-equal, and asserted so
-  float32 vs oracle, four shapes      5.3e-7 ... 5.9e-7 rms, per-row and folded
+  float32 vs oracle, four shapes      5.3e-7 ... 5.9e-7 rms
   sampling vs golden, every x_t       <= 1.8e-7 rms
   SDDM.forward vs oracle              5.4e-7 rms
-The per-row path is the default at every length; the folded kernel is slower and is
-kept and tested here.  Only runs with SDDM_WU_FOLD_ALL=1 reach wu_fold_kernel: the "fold_all" child
-process and the "fold_all" networks of _net; "default" and "per_row" run the same kernels.
+Every layer at every length runs wu_conv_kernel per batch row.  Most tests share one network per
+dtype in this process; the two *_by_path tests read the forwards of one child process
+(_wu_paths_child.py), in which the library is loaded and a context configured by those forwards
+alone.  The output bits of this network are pinned by test_gpu_seq_digests.py.
 """
 import functools
 import json
@@ -51,28 +51,15 @@ def _params():
     return make_params(O.param_shapes(), 0)
 
 
-def _net(dtype="float32", path="default"):
-    """One facade network per (dtype, path), shared by the tests (its weights never change).  The
-    library reads the path knob when a context is configured, i.e. at the network's first forward:
-    path "fold_all" sets SDDM_WU_FOLD_ALL around a first forward, so that network's short levels run
-    the batch-folded kernel whatever the default table says."""
-    if (dtype, path) not in _NETS:
+def _net(dtype="float32"):
+    """One facade network per dtype, shared by the tests (its weights never change)."""
+    if dtype not in _NETS:
         import model.network as NW
         n = NW.Waveunet(**O.ARGS)
         n.load_state_dict({k: torch.from_numpy(v) for k, v in _params().items()})
         n.compute_dtype = dtype
-        n = n.cuda()
-        old = {k: os.environ.pop(k, None) for k in ("SDDM_WU_NO_FOLD", "SDDM_WU_FOLD_ALL")}
-        try:
-            if path == "fold_all":
-                os.environ["SDDM_WU_FOLD_ALL"] = "1"
-            z = torch.zeros(1, 1, 2048, device="cuda")
-            n(z, z, torch.ones(1, device="cuda"))
-        finally:
-            os.environ.pop("SDDM_WU_FOLD_ALL", None)
-            os.environ.update({k: v for k, v in old.items() if v is not None})
-        _NETS[(dtype, path)] = n
-    return _NETS[(dtype, path)]
+        _NETS[dtype] = n.cuda()
+    return _NETS[dtype]
 
 
 def _model(mode="original", noise_condition="sqrt_alpha_bar", dtype="float32", sched=SCHED):
@@ -107,7 +94,7 @@ def _clamped(x):
 
 @functools.lru_cache(maxsize=None)
 def _oracle_case(B, N):
-    """Inputs and the oracle's output of one shape, computed once for both paths."""
+    """Inputs and the oracle's output of one shape, computed once."""
     cond, x_t, nl = _inputs(B, N, seed=31)
     return cond, x_t, nl, O.forward(_params(), cond, x_t, nl)
 
@@ -139,54 +126,45 @@ def test_forward_matches_reference(torch_cuda, dtype):
         assert err / rms(ref, 0) <= _bar16(dtype, emu)
 
 
-# ---- the two paths of the short levels, each in a fresh process (the knob is read at configure time)
+# ---- the forward in a fresh process.  Explicit ids here and below ("-per_row", "-default") keep the
+# ids stable that these cases are recorded under
 HERE = os.path.dirname(os.path.abspath(__file__))
 _CHILD = {}
 _CHILD_FAILED = []
 
 
-_KNOBS = {"per_row": "SDDM_WU_NO_FOLD", "fold_all": "SDDM_WU_FOLD_ALL"}
-
-
-def _path_run(path):
-    """The arrays of one child (spawned once per module): "per_row" (SDDM_WU_NO_FOLD=1; the default
-    folds nothing either, so these are the kernels of the in-process tests) or "fold_all"
-    (SDDM_WU_FOLD_ALL=1: the only runs that reach wu_fold_kernel).  After a child that faulted, was
-    killed or failed, no further child is started."""
-    if path in _CHILD:
-        return _CHILD[path]
+def _child_run():
+    """The arrays of the child (spawned once per module).  After a child that faulted, was killed or
+    failed, no further child is started."""
+    if _CHILD:
+        return _CHILD
     if _CHILD_FAILED:
         pytest.fail(_CHILD_FAILED[0])
-    env = {k: v for k, v in os.environ.items() if k not in _KNOBS.values()}
-    env[_KNOBS[path]] = "1"
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "out.npz")
         try:
-            r = subprocess.run([sys.executable, os.path.join(HERE, "_wu_paths_child.py"), out], env=env, timeout=120,
+            r = subprocess.run([sys.executable, os.path.join(HERE, "_wu_paths_child.py"), out], timeout=120,
                                stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         except subprocess.TimeoutExpired:
-            _CHILD_FAILED.append(f"path child ({path}) was killed at its 120 s limit")
+            _CHILD_FAILED.append("the child process was killed at its 120 s limit")
             pytest.fail(_CHILD_FAILED[0])
         if r.returncode != 0:
-            _CHILD_FAILED.append(f"path child ({path}) ended with status {r.returncode}:\n{r.stdout[-2000:]}")
+            _CHILD_FAILED.append(f"the child process ended with status {r.returncode}:\n{r.stdout[-2000:]}")
             pytest.fail(_CHILD_FAILED[0])
         with np.load(out, allow_pickle=False) as z:
-            _CHILD[path] = {k: z[k] for k in z.files}
-    return _CHILD[path]
+            _CHILD.update({k: z[k] for k in z.files})
+    return _CHILD
 
 
-@pytest.mark.parametrize("path", ["per_row", "fold_all"])
-@pytest.mark.parametrize("dtype", ["float32", "bfloat16", "float16"])
-def test_forward_matches_reference_by_path(torch_cuda, dtype, path):
-    """The golden forward with the knob set, each path in its own process, at the bars of
-    test_forward_matches_reference.  per_row: every layer through wu_conv_kernel, complete on its own
-    (the default folds nothing, so this repeats the in-process test's kernels with the knob).
-    fold_all: levels 5 to 11 (64 ... 1 positions) through wu_fold_kernel."""
+@pytest.mark.parametrize("dtype", [pytest.param(d, id=d + "-per_row") for d in ("float32", "bfloat16", "float16")])
+def test_forward_matches_reference_by_path(torch_cuda, dtype):
+    """The golden forward in a process of its own, at the bars of test_forward_matches_reference:
+    every layer through wu_conv_kernel, complete on its own."""
     z = golden("waveunet.npz")
     ref = z["fw/eps"]
-    eps = _path_run(path)[f"fw/{dtype}"]
+    eps = _child_run()[f"fw/{dtype}"]
     rel = rms(eps, ref) / rms(ref, 0)
-    print(f"Waveunet {dtype} {path}: relative rms vs reference {rel:.3e}")
+    print(f"Waveunet {dtype}, child process: relative rms vs reference {rel:.3e}")
     assert np.isfinite(eps).all()
     if dtype == "float32":
         assert rms(eps, ref) <= 1e-4 * _gate(ref)
@@ -195,47 +173,29 @@ def test_forward_matches_reference_by_path(torch_cuda, dtype, path):
         assert rel <= _bar16(dtype, rms(emu, ref) / rms(ref, 0))
 
 
-@pytest.mark.parametrize("path", ["per_row", "fold_all"])
-def test_odd_shape_matches_oracle_by_path(torch_cuda, path):
-    """B = 3, N = 6144 (lengths 96 ... 3) in float32 with the knob set, in the path's own process."""
+@pytest.mark.parametrize("shape", [pytest.param((3, 6144), id="per_row")])
+def test_odd_shape_matches_oracle_by_path(torch_cuda, shape):
+    """B = 3, N = 6144 (lengths 96 ... 3) in float32, in the child process."""
     cond, x_t, nl = child.odd_inputs()
+    assert cond.shape == (shape[0], 1, shape[1])
     odd = O.forward(_params(), cond, x_t, nl)
-    err = rms(_path_run(path)["odd/float32"], odd)
-    print(f"Waveunet {path} B=3 N=6144: rms vs oracle {err:.3e}")
+    err = rms(_child_run()["odd/float32"], odd)
+    print(f"Waveunet, child process, B=3 N=6144: rms vs oracle {err:.3e}")
     assert err <= 1e-4 * _gate(odd)
 
 
-@pytest.mark.parametrize("dtype", ["bfloat16", "float16"])
-def test_folded_path_is_bit_equal_to_per_row_path(torch_cuda, dtype):
-    """Same dtype, same inputs, each path in its own process.  wu_fold_kernel runs the K loop of
-    every output in wu_conv_kernel's order and adds the GroupNorm sums in the per-row path's order
-    (row_sum16's tree per 32-position slot, the second square by FMA, wu_gn_finalize's fp64 tree),
-    so the two paths give the same bits, and that is what is asserted.  Equality implies the bound
-    the comparison was given, a quarter of the per-row path's own error against the fp32 golden;
-    the figures are printed so that a lost equality shows how far the paths drifted."""
-    ref = golden("waveunet.npz")["fw/eps"]
-    row, fold = _path_run("per_row")[f"fw/{dtype}"], _path_run("fold_all")[f"fw/{dtype}"]
-    own, diff = rms(row, ref) / rms(ref, 0), rms(fold, row) / rms(ref, 0)
-    print(f"Waveunet {dtype}: fold_all vs per-row relative rms {diff:.3e}, {int((fold != row).sum())} of {fold.size} "
-          f"values differ; per-row vs golden {own:.3e} (a quarter: {0.25 * own:.3e})")
-    assert np.isfinite(fold).all()
-    assert np.array_equal(fold, row)
-
-
-@pytest.mark.parametrize("path", ["default", "fold_all"])
-@pytest.mark.parametrize("B,N", [(3, 6144), (5, 2048), (1, 2048), (2, 4096)])
-def test_forward_matches_oracle(torch_cuda, B, N, path):
-    """Shapes at which the short levels can go wrong, on the default path and with the folded kernel
-    at every short length.  B=3, N=6144: lengths 96, 48, 24, 12, 6, 3 -- no
+@pytest.mark.parametrize("B,N", [pytest.param(B, N, id=f"{B}-{N}-default") for B, N in ((3, 6144), (5, 2048), (1, 2048), (2, 4096))])
+def test_forward_matches_oracle(torch_cuda, B, N):
+    """Shapes at which the short levels can go wrong.  B=3, N=6144: lengths 96, 48, 24, 12, 6, 3 -- no
     powers of two, rows straddle or under-fill a 128-column tile, odd batch.  B=5, N=2048: 320
     columns of rows at L = 64.  B=1: level passed as [B, 1, 1].  B=2, N=4096."""
     cond, x_t, nl, ref = _oracle_case(B, N)
     assert _clamped(ref) <= 0.25
     level = torch.from_numpy(nl).cuda()
-    eps = _net("float32", path)(torch.from_numpy(cond).cuda(), torch.from_numpy(x_t).cuda(), level.reshape(B, 1, 1) if B == 1 else level)
+    eps = _net("float32")(torch.from_numpy(cond).cuda(), torch.from_numpy(x_t).cuda(), level.reshape(B, 1, 1) if B == 1 else level)
     assert tuple(eps.shape) == (B, 1, N)
     err = rms(eps.cpu().numpy(), ref)
-    print(f"Waveunet {path} B={B} N={N}: rms vs oracle {err:.3e} (ref rms {rms(ref, 0):.3f}, clamped {_clamped(ref):.3f})")
+    print(f"Waveunet B={B} N={N}: rms vs oracle {err:.3e} (ref rms {rms(ref, 0):.3f}, clamped {_clamped(ref):.3f})")
     assert err <= 1e-4 * _gate(ref)
 
 
@@ -296,11 +256,10 @@ def test_row_sharding_is_bit_identical(torch_cuda):
     assert torch.equal(full, torch.cat([a, b]))
 
 
-@pytest.mark.parametrize("path", ["default", "fold_all"])
-@pytest.mark.parametrize("N", [2048, 6144])
-def test_rows_are_independent_of_the_batch(torch_cuda, N, path):
+@pytest.mark.parametrize("N", [pytest.param(N, id=f"{N}-default") for N in (2048, 6144)])
+def test_rows_are_independent_of_the_batch(torch_cuda, N):
     """Row b of a B = 5 forward equals the same clip run alone, bit for bit (bfloat16)."""
-    net = _net("bfloat16", path)
+    net = _net("bfloat16")
     cond, x_t, nl = (torch.from_numpy(a).cuda() for a in _inputs(5, N, seed=2))
     full = net(cond, x_t, nl)
     assert torch.isfinite(full).all() and float(full.abs().max()) > 0
