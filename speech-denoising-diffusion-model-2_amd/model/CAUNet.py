@@ -7,10 +7,9 @@ unchanged; ``nn.Conv2d``, ``nn.LayerNorm``, ``nn.PReLU``, ``nn.GRU`` and ``nn.Mu
 serve as holders.  ``forward`` never computes in torch: ``CAUNet.forward`` runs the whole denoiser in
 libsddm_hip and ``Dual_Transformer.forward`` runs the block alone (sddm_dual_transformer).
 """
-import torch
 from torch import nn
 
-import sddm_hip
+from ._facade import DualTransformerFacade, LenientFacade
 from .UNetModified2 import PositionalEncoding, SignalToFrames
 from .UNetTST import TransformerEncoderLayer
 
@@ -29,13 +28,16 @@ class FeatureWiseAffine(nn.Module):
                                         nn.Linear(n, out_channels * (1 + self.use_affine_level)))
 
 
-class Dual_Transformer(nn.Module):
+class Dual_Transformer(DualTransformerFacade):
     """Conv1x1 + PReLU(input_size / 2), num_layers x (row encoder, GroupNorm, residual, column encoder,
     GroupNorm, residual), Conv1x1 + PReLU(output_size) (CAUNet.py:152-201).  The HIP kernels are built
     for input_size = output_size = 64; dim2 and dim1 are free."""
 
+    network_type = "CAUNet"
+
     def __init__(self, input_size, output_size, dropout=0, num_layers=1):
         super().__init__()
+        self._init_facade({"n_TSTB": num_layers}, 704)
         self.input_size, self.output_size, self.num_layers = input_size, output_size, num_layers
         d = input_size // 2
         self.input = nn.Sequential(nn.Conv2d(input_size, d, kernel_size=1), nn.PReLU(d))
@@ -49,9 +51,6 @@ class Dual_Transformer(nn.Module):
             self.row_norm.append(nn.GroupNorm(1, d, eps=1e-8))
             self.col_norm.append(nn.GroupNorm(1, d, eps=1e-8))
         self.output = nn.Sequential(nn.Conv2d(d, output_size, 1), nn.PReLU(output_size))
-        self.compute_dtype = "float32"
-        self._ctx = None
-        self._ctx_key = None
 
     def library_config(self):
         """A CAUNet context around this block (only its mid.* parameters get loaded)."""
@@ -60,31 +59,7 @@ class Dual_Transformer(nn.Module):
                                       f"{self.input_size} / {self.output_size}")
         if self.num_layers < 1:
             raise NotImplementedError(f"CAUNet Dual_Transformer on HIP: num_layers {self.num_layers} (at least 1)")
-        return {"arch": {"type": "SDDM", "args": {}},
-                "diffusion": {"type": "GaussianDiffusion", "args": {"schedule": "linear", "n_timestep": 1}},
-                "network": {"type": "CAUNet", "args": {"n_TSTB": self.num_layers}},
-                "num_samples": 704}
-
-    def _context(self, device):
-        sd = self.state_dict()
-        key = (device.index or 0, self.compute_dtype) + tuple((k, v.data_ptr(), v._version) for k, v in sd.items())
-        if self._ctx is None or self._ctx_key != key:
-            ctx = sddm_hip.Context(self.library_config(), device.index or 0, self.compute_dtype)
-            ctx.load_state_dict({"mid." + k: v for k, v in sd.items()})
-            self._ctx, self._ctx_key = ctx, key
-        return self._ctx
-
-    @torch.no_grad()
-    def forward(self, input):
-        """input [b, c, dim2, dim1] -> [b, c, dim2, dim1]."""
-        if not input.is_cuda:
-            raise RuntimeError("Dual_Transformer runs on the HIP device; move the input to cuda")
-        x = input.contiguous().float()
-        if x.dim() != 4 or x.shape[1] != self.input_size:
-            raise AssertionError(f"Dual_Transformer expects [b, {self.input_size}, dim2, dim1], got {tuple(x.shape)}")
-        out = torch.empty((x.shape[0], self.output_size) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
-        self._context(x.device).dual_transformer(x, out)
-        return out
+        return super().library_config()
 
 
 class SPConvTranspose2d(nn.Module):
@@ -127,7 +102,10 @@ class DecodeLayer(nn.Module):
                                       nn.LayerNorm(frame_length * 2), nn.PReLU(n_out_channels))
 
 
-class CAUNet(nn.Module):
+class CAUNet(LenientFacade):
+    """forward(x, y_t, noise_level): the noise level is a vector of B entries (the reference's squeeze()
+    breaks at B = 1)."""
+
     def __init__(self, num_samples, inner_channel=64, n_encode_layers=4, dense_depth=3, n_TSTB=6, segment_len=128,
                  segment_stride=64, use_affine_level=False):
         super().__init__()
@@ -140,8 +118,7 @@ class CAUNet(nn.Module):
             raise NotImplementedError(f"CAUNet on HIP: n_TSTB at least 1, got {n_TSTB}")
         if not isinstance(use_affine_level, bool):
             raise NotImplementedError(f"CAUNet on HIP: use_affine_level false or true, got {use_affine_level!r}")
-        self.num_samples = num_samples
-        self.config_args = dict(given, n_TSTB=n_TSTB, use_affine_level=use_affine_level)
+        self._init_facade(dict(given, n_TSTB=n_TSTB, use_affine_level=use_affine_level), num_samples)
         self.noise_encoding = PositionalEncoding(inner_channel)
         self.segment = SignalToFrames(num_samples, segment_len, segment_stride)          # asserts (num_samples - 128) % 64 == 0
         self.first_conv = nn.Conv2d(2, inner_channel, kernel_size=(1, 1), stride=(1, 1))
@@ -156,36 +133,3 @@ class CAUNet(nn.Module):
             self.ups.append(DecodeLayer(inner_channel, length, inner_channel, inner_channel, dense_depth, use_affine_level))
             length *= 2
         self.final_conv = nn.Conv2d(inner_channel, 1, kernel_size=(1, 1))
-        self.compute_dtype = "float32"
-        self._ctx = None
-        self._ctx_key = None
-
-    def library_config(self):
-        return {"arch": {"type": "SDDM", "args": {}},
-                "diffusion": {"type": "GaussianDiffusion", "args": {"schedule": "linear", "n_timestep": 1}},
-                "network": {"type": "CAUNet", "args": self.config_args},
-                "num_samples": self.num_samples}
-
-    def _context(self, device):
-        sd = self.state_dict()
-        key = (device.index or 0, self.compute_dtype) + tuple((k, v.data_ptr(), v._version) for k, v in sd.items())
-        if self._ctx is None or self._ctx_key != key:
-            ctx = sddm_hip.Context(self.library_config(), device.index or 0, self.compute_dtype)
-            ctx.load_state_dict(sd)
-            self._ctx, self._ctx_key = ctx, key
-        return self._ctx
-
-    @torch.no_grad()
-    def forward(self, x, y_t, noise_level):
-        """x: condition [B,1,T], y_t: [B,1,T], noise_level: [B,1,1] -> eps [B,1,T].  The noise level
-        is a vector of B entries (the reference's squeeze() breaks at B = 1)."""
-        if not x.is_cuda:
-            raise RuntimeError("CAUNet runs on the HIP device; move inputs to cuda")
-        x = x.contiguous().float()
-        y_t = y_t.contiguous().float()
-        nl = noise_level.reshape(-1).contiguous().float()
-        if nl.numel() == 1 and x.shape[0] > 1:
-            nl = nl.expand(x.shape[0]).contiguous()
-        out = torch.empty_like(y_t)
-        self._context(x.device).network_forward(x, y_t, nl, out)
-        return out

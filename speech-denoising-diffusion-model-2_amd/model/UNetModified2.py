@@ -9,7 +9,7 @@ torch: it hands the weights to libsddm_hip and runs the whole denoiser as HIP ke
 import torch
 from torch import nn
 
-import sddm_hip
+from ._facade import LenientFacade
 
 
 class SignalToFrames(nn.Module):
@@ -78,15 +78,14 @@ class Downsample(nn.Module):
         self.conv = nn.Conv2d(dim, dim, 3, 2, 1)
 
 
-class UNetModified2(nn.Module):
+class UNetModified2(LenientFacade):
     def __init__(self, num_samples, in_channel=2, out_channel=1, inner_channel=32, norm_groups=32,
                  channel_mults=(1, 2, 3, 4, 5), res_blocks=3, dropout=0, segment_len=128, segment_stride=64):
         super().__init__()
-        self.num_samples = num_samples
-        self.config_args = {"in_channel": in_channel, "out_channel": out_channel, "inner_channel": inner_channel,
-                            "norm_groups": norm_groups, "channel_mults": list(channel_mults),
-                            "res_blocks": res_blocks, "dropout": dropout, "segment_len": segment_len,
-                            "segment_stride": segment_stride}
+        self._init_facade({"in_channel": in_channel, "out_channel": out_channel, "inner_channel": inner_channel,
+                           "norm_groups": norm_groups, "channel_mults": list(channel_mults),
+                           "res_blocks": res_blocks, "dropout": dropout, "segment_len": segment_len,
+                           "segment_stride": segment_stride}, num_samples)
         self.segment = SignalToFrames(num_samples, segment_len, segment_stride)
         E = inner_channel
         self.noise_level_mlp = nn.Sequential(PositionalEncoding(E), nn.Linear(E, E * 4), Swish(),
@@ -116,35 +115,3 @@ class UNetModified2(nn.Module):
                 cin = cout
         self.ups = nn.ModuleList(ups)
         self.final_conv = Block(cout, out_channel, groups=norm_groups)
-        self.compute_dtype = "float32"
-        self._ctx = None
-        self._ctx_key = None
-
-    def library_config(self):
-        return {"arch": {"type": "SDDM", "args": {}},
-                "diffusion": {"type": "GaussianDiffusion", "args": {"schedule": "linear", "n_timestep": 1}},
-                "network": {"type": "UNetModified2", "args": self.config_args},
-                "num_samples": self.num_samples}
-
-    def _context(self, device):
-        sd = self.state_dict()
-        key = (device.index or 0, self.compute_dtype) + tuple((k, v.data_ptr(), v._version) for k, v in sd.items())
-        if self._ctx is None or self._ctx_key != key:
-            ctx = sddm_hip.Context(self.library_config(), device.index or 0, self.compute_dtype)
-            ctx.load_state_dict(sd)
-            self._ctx, self._ctx_key = ctx, key
-        return self._ctx
-
-    @torch.no_grad()
-    def forward(self, x, y_t, diffusion_step):
-        """x: condition [B,1,T], y_t: [B,1,T], diffusion_step: noise level [B,1,1] -> eps [B,1,T]."""
-        if not x.is_cuda:
-            raise RuntimeError("UNetModified2 runs on the HIP device; move inputs to cuda")
-        x = x.contiguous().float()
-        y_t = y_t.contiguous().float()
-        nl = diffusion_step.reshape(-1).contiguous().float()
-        if nl.numel() == 1 and x.shape[0] > 1:
-            nl = nl.expand(x.shape[0]).contiguous()
-        out = torch.empty_like(y_t)
-        self._context(x.device).network_forward(x, y_t, nl, out)
-        return out

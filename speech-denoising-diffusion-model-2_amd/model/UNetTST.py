@@ -7,10 +7,9 @@ loads unchanged; ``nn.MultiheadAttention``, ``nn.GRU``, ``nn.LayerNorm``, ``nn.G
 ``nn.PReLU`` serve as holders.  ``forward`` never computes in torch: ``UNetTST.forward`` runs the whole
 denoiser in libsddm_hip and ``Dual_Transformer.forward`` runs the block alone (sddm_dual_transformer).
 """
-import torch
 from torch import nn
 
-import sddm_hip
+from ._facade import DualTransformerFacade, LenientFacade
 from .UNetModified2 import (Block, Downsample, PositionalEncoding, ResnetBlock, SignalToFrames, Swish,  # noqa: F401
                             Upsample)
 
@@ -34,13 +33,16 @@ class TransformerEncoderLayer(nn.Module):
         self.dropout2 = nn.Dropout(dropout)
 
 
-class Dual_Transformer(nn.Module):
+class Dual_Transformer(DualTransformerFacade):
     """Conv1x1 + PReLU, num_layers x (row encoder, GroupNorm, residual, column encoder, GroupNorm,
     residual), Conv1x1 + PReLU (UNetTST.py:184-233).  The HIP kernel is built for input_size =
     output_size = 160 and at most 64 positions (dim2 * dim1)."""
 
+    network_type = "UNetTST"
+
     def __init__(self, input_size, output_size, dropout=0, num_layers=1):
         super().__init__()
+        self._init_facade({"res_blocks": 1, "n_TSTB": num_layers}, 2112)
         self.input_size, self.output_size, self.num_layers = input_size, output_size, num_layers
         d = input_size // 2
         self.input = nn.Sequential(nn.Conv2d(input_size, d, kernel_size=1), nn.PReLU())
@@ -54,51 +56,23 @@ class Dual_Transformer(nn.Module):
             self.row_norm.append(nn.GroupNorm(1, d, eps=1e-8))
             self.col_norm.append(nn.GroupNorm(1, d, eps=1e-8))
         self.output = nn.Sequential(nn.Conv2d(d, output_size, 1), nn.PReLU())
-        self.compute_dtype = "float32"
-        self._ctx = None
-        self._ctx_key = None
 
     def library_config(self):
         """A UNetTST context around this block (only its mid.* parameters get loaded)."""
         if self.input_size != 160 or self.output_size != 160:
             raise NotImplementedError(f"Dual_Transformer on HIP: input_size / output_size 160, got "
                                       f"{self.input_size} / {self.output_size}")
-        return {"arch": {"type": "SDDM", "args": {}},
-                "diffusion": {"type": "GaussianDiffusion", "args": {"schedule": "linear", "n_timestep": 1}},
-                "network": {"type": "UNetTST", "args": {"res_blocks": 1, "n_TSTB": self.num_layers}},
-                "num_samples": 2112}
-
-    def _context(self, device):
-        sd = self.state_dict()
-        key = (device.index or 0, self.compute_dtype) + tuple((k, v.data_ptr(), v._version) for k, v in sd.items())
-        if self._ctx is None or self._ctx_key != key:
-            ctx = sddm_hip.Context(self.library_config(), device.index or 0, self.compute_dtype)
-            ctx.load_state_dict({"mid." + k: v for k, v in sd.items()})
-            self._ctx, self._ctx_key = ctx, key
-        return self._ctx
-
-    @torch.no_grad()
-    def forward(self, input):
-        """input [b, c, dim2, dim1] -> [b, c, dim2, dim1]."""
-        if not input.is_cuda:
-            raise RuntimeError("Dual_Transformer runs on the HIP device; move the input to cuda")
-        x = input.contiguous().float()
-        if x.dim() != 4 or x.shape[1] != self.input_size:
-            raise AssertionError(f"Dual_Transformer expects [b, {self.input_size}, dim2, dim1], got {tuple(x.shape)}")
-        out = torch.empty((x.shape[0], self.output_size) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
-        self._context(x.device).dual_transformer(x, out)
-        return out
+        return super().library_config()
 
 
-class UNetTST(nn.Module):
+class UNetTST(LenientFacade):
     def __init__(self, num_samples, in_channel=2, out_channel=1, inner_channel=32, norm_groups=32,
                  channel_mults=(1, 2, 3, 4, 5), n_TSTB=6, res_blocks=3, dropout=0, segment_len=128, segment_stride=64):
         super().__init__()
-        self.num_samples = num_samples
-        self.config_args = {"in_channel": in_channel, "out_channel": out_channel, "inner_channel": inner_channel,
-                            "norm_groups": norm_groups, "channel_mults": list(channel_mults), "n_TSTB": n_TSTB,
-                            "res_blocks": res_blocks, "dropout": dropout, "segment_len": segment_len,
-                            "segment_stride": segment_stride}
+        self._init_facade({"in_channel": in_channel, "out_channel": out_channel, "inner_channel": inner_channel,
+                           "norm_groups": norm_groups, "channel_mults": list(channel_mults), "n_TSTB": n_TSTB,
+                           "res_blocks": res_blocks, "dropout": dropout, "segment_len": segment_len,
+                           "segment_stride": segment_stride}, num_samples)
         self.segment = SignalToFrames(num_samples, segment_len, segment_stride)
         E = inner_channel
         self.noise_level_mlp = nn.Sequential(PositionalEncoding(E), nn.Linear(E, E * 4), Swish(),
@@ -128,35 +102,3 @@ class UNetTST(nn.Module):
                 cin = cout
         self.ups = nn.ModuleList(ups)
         self.final_conv = Block(cout, out_channel, groups=norm_groups)
-        self.compute_dtype = "float32"
-        self._ctx = None
-        self._ctx_key = None
-
-    def library_config(self):
-        return {"arch": {"type": "SDDM", "args": {}},
-                "diffusion": {"type": "GaussianDiffusion", "args": {"schedule": "linear", "n_timestep": 1}},
-                "network": {"type": "UNetTST", "args": self.config_args},
-                "num_samples": self.num_samples}
-
-    def _context(self, device):
-        sd = self.state_dict()
-        key = (device.index or 0, self.compute_dtype) + tuple((k, v.data_ptr(), v._version) for k, v in sd.items())
-        if self._ctx is None or self._ctx_key != key:
-            ctx = sddm_hip.Context(self.library_config(), device.index or 0, self.compute_dtype)
-            ctx.load_state_dict(sd)
-            self._ctx, self._ctx_key = ctx, key
-        return self._ctx
-
-    @torch.no_grad()
-    def forward(self, x, y_t, noise_level):
-        """x: condition [B,1,T], y_t: [B,1,T], noise_level: [B,1,1] -> eps [B,1,T]."""
-        if not x.is_cuda:
-            raise RuntimeError("UNetTST runs on the HIP device; move inputs to cuda")
-        x = x.contiguous().float()
-        y_t = y_t.contiguous().float()
-        nl = noise_level.reshape(-1).contiguous().float()
-        if nl.numel() == 1 and x.shape[0] > 1:
-            nl = nl.expand(x.shape[0]).contiguous()
-        out = torch.empty_like(y_t)
-        self._context(x.device).network_forward(x, y_t, nl, out)
-        return out

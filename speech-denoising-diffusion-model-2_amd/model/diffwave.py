@@ -12,7 +12,7 @@ from math import sqrt  # noqa: F401  (reference import surface)
 import torch
 from torch import nn
 
-import sddm_hip
+from ._facade import Facade
 
 
 def Conv1d(*args, **kwargs):
@@ -59,14 +59,15 @@ class ResidualBlock(nn.Module):
         self.output_residual = Conv1d(residual_channels, residual_channels, 1)
 
 
-class DiffWave(nn.Module):
+class DiffWave(Facade):
+    arch = ("SDDM_spectrogram", {"hop_samples": 256})
+
     def __init__(self, num_samples, num_timesteps, freq_bins, residual_channels=64, residual_layers=30,
                  dilation_cycle_length=10):
         super().__init__()
-        self.num_samples = num_samples
+        self._init_facade({"residual_channels": residual_channels, "residual_layers": residual_layers,
+                           "dilation_cycle_length": dilation_cycle_length, "freq_bins": freq_bins}, num_samples)
         self.freq_bins = freq_bins
-        self.config_args = {"residual_channels": residual_channels, "residual_layers": residual_layers,
-                            "dilation_cycle_length": dilation_cycle_length, "freq_bins": freq_bins}
         self.input_projection = Conv1d(1, residual_channels, 1)
         self.diffusion_embedding = DiffusionEmbedding()
         self.spectrogram_upsampler = SpectrogramUpsampler(freq_bins)
@@ -76,29 +77,12 @@ class DiffWave(nn.Module):
         self.skip_projection = Conv1d(residual_channels, residual_channels, 1)
         self.output_projection = Conv1d(residual_channels, 1, 1)
         nn.init.zeros_(self.output_projection.weight)                # diffwave.py:131
-        self.compute_dtype = "float32"
-        self._ctx = None
-        self._ctx_key = None
 
     def library_params(self):
         """state_dict + the fp32 embedding vector (a plain attribute in the reference)."""
         sd = dict(self.state_dict())
         sd["diffusion_embedding.embedding_vector"] = self.diffusion_embedding.embedding_vector.float()
         return sd
-
-    def library_config(self):
-        return {"arch": {"type": "SDDM_spectrogram", "args": {"hop_samples": 256}},
-                "diffusion": {"type": "GaussianDiffusion", "args": {"schedule": "linear", "n_timestep": 1}},
-                "network": {"type": "DiffWave", "args": self.config_args}, "num_samples": self.num_samples}
-
-    def _context(self, device):
-        sd = self.library_params()
-        key = (device.index or 0, self.compute_dtype) + tuple((k, v.data_ptr(), v._version) for k, v in sd.items())
-        if self._ctx is None or self._ctx_key != key:
-            ctx = sddm_hip.Context(self.library_config(), device.index or 0, self.compute_dtype)
-            ctx.load_state_dict(sd)
-            self._ctx, self._ctx_key = ctx, key
-        return self._ctx
 
     @torch.no_grad()
     def forward(self, spectrogram, audio, diffusion_step):

@@ -17,6 +17,5 @@ from .UNetModified2 import UNetModified2  # noqa: F401
 from .UNetTST import Dual_Transformer, UNetTST  # noqa: F401
 from .diffwave import DiffWave  # noqa: F401
 from .wavegrad import DenoiseWaveGrad1, DenoiseWaveGrad3, WaveGrad  # noqa: F401
-from .waveunet import Waveunet  # noqa: F401
-from .waveunet2 import Waveunet2  # noqa: F401
+from .waveunet import Waveunet, Waveunet2  # noqa: F401
 from .waveunet3 import Waveunet3  # noqa: F401

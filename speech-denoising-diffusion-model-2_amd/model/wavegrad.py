@@ -26,7 +26,7 @@ from math import log as ln  # noqa: F401  (reference import surface)
 import torch
 from torch import nn
 
-import sddm_hip
+from ._facade import Facade, StrictFacade
 from .diffwave import check_spectrogram
 
 
@@ -84,7 +84,7 @@ class DBlock(nn.Module):
             Conv1d(hidden_size, hidden_size, 3, dilation=4, padding=4)])
 
 
-class WaveGrad(nn.Module):
+class WaveGrad(Facade):
     """wavegrad.py:140-179.  The reference constructor takes no arguments; the keyword arguments
     ConfigParser.init_obj adds (num_samples, freq_bins, num_timesteps) are accepted and ignored."""
 
@@ -113,25 +113,11 @@ class WaveGrad(nn.Module):
             UBlock(128, 128, 2, [1, 2, 4, 8])])
         self.first_conv = Conv1d(128, 768, 3, padding=1)
         self.last_conv = Conv1d(128, 1, 3, padding=1)
-        self.config_args = {}
-        self.num_samples = -1
-        self.compute_dtype = "float32"
-        self._ctx = None
-        self._ctx_key = None
+        self._init_facade({})
 
-    def library_config(self):
-        return {"arch": {"type": "SDDM_spectrogram", "args": {"hop_samples": self.hop_samples}},
-                "diffusion": {"type": "GaussianDiffusion", "args": {"schedule": "linear", "n_timestep": 1}},
-                "network": {"type": "WaveGrad", "args": {}}, "num_samples": -1}
-
-    def _context(self, device):
-        sd = dict(self.state_dict())
-        key = (device.index or 0, self.compute_dtype) + tuple((k, v.data_ptr(), v._version) for k, v in sd.items())
-        if self._ctx is None or self._ctx_key != key:
-            ctx = sddm_hip.Context(self.library_config(), device.index or 0, self.compute_dtype)
-            ctx.load_state_dict(sd)
-            self._ctx, self._ctx_key = ctx, key
-        return self._ctx
+    @property
+    def arch(self):
+        return "SDDM_spectrogram", {"hop_samples": self.hop_samples}
 
     @torch.no_grad()
     def forward(self, spectrogram, audio, noise_scale):
@@ -151,47 +137,7 @@ class WaveGrad(nn.Module):
         return torch.squeeze(out)
 
 
-class _WaveformDenoiser(nn.Module):
-    """Shared facade of the waveform-conditioned variants: the subclasses build the parameter tree
-    (reference attribute names) and name their hop.  The reference constructors take no arguments;
-    the keyword arguments ConfigParser.init_obj adds (num_samples) are accepted and ignored."""
-
-    hop_samples = None
-
-    def _init_facade(self):
-        self.config_args = {}
-        self.num_samples = -1
-        self.compute_dtype = "float32"
-        self._ctx = None
-        self._ctx_key = None
-
-    def library_config(self):
-        return {"arch": {"type": "SDDM", "args": {}},
-                "diffusion": {"type": "GaussianDiffusion", "args": {"schedule": "linear", "n_timestep": 1}},
-                "network": {"type": type(self).__name__, "args": {}}, "num_samples": -1}
-
-    _context = WaveGrad._context
-
-    @torch.no_grad()
-    def forward(self, x, y_t, noise_level):
-        """x (noisy waveform) and y_t [B, 1, N], N a positive multiple of hop_samples; noise_level
-        with B elements (any shape) -> eps [B, 1, N] (wavegrad.py:226-242, 341-353)."""
-        if not y_t.is_cuda:
-            raise RuntimeError(f"{type(self).__name__} runs on the HIP device; move the tensors to cuda")
-        B = y_t.shape[0]
-        cond = x.reshape(B, 1, -1).contiguous().float()
-        yt = y_t.reshape(B, 1, -1).contiguous().float()
-        if cond.shape != yt.shape:
-            raise RuntimeError(f"condition {tuple(x.shape)} and y_t {tuple(y_t.shape)} differ in size")
-        nl = noise_level.reshape(-1).contiguous().float()
-        if nl.numel() != B:
-            raise RuntimeError(f"noise_level has {nl.numel()} elements for batch {B}")
-        out = torch.empty_like(yt)
-        self._context(yt.device).network_forward(cond, yt, nl, out)
-        return out
-
-
-class DenoiseWaveGrad1(_WaveformDenoiser):
+class DenoiseWaveGrad1(StrictFacade):
     """wavegrad.py:184-242: the condition x goes down its own DBlock ladder (downsample_x) to the
     512-channel input of the first UBlock; y_t's ladder feeds the FiLMs."""
 
@@ -225,10 +171,10 @@ class DenoiseWaveGrad1(_WaveformDenoiser):
             UBlock(256, 128, 2, [1, 2, 4, 8]),
             UBlock(128, 128, 2, [1, 2, 4, 8])])
         self.last_conv = Conv1d(128, 1, 3, padding=1)
-        self._init_facade()
+        self._init_facade({})
 
 
-class DenoiseWaveGrad3(_WaveformDenoiser):
+class DenoiseWaveGrad3(StrictFacade):
     """wavegrad.py:307-353: cat([y_t, x]) enters one ladder; an extra bottleneck DBlock feeds the
     first UBlock."""
 
@@ -256,4 +202,4 @@ class DenoiseWaveGrad3(_WaveformDenoiser):
             UBlock(256, 128, 2, [1, 2, 4, 8]),
             UBlock(128, 128, 2, [1, 2, 4, 8])])
         self.last_conv = Conv1d(128, 1, 3, padding=1)
-        self._init_facade()
+        self._init_facade({})

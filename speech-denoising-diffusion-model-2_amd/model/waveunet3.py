@@ -8,8 +8,9 @@ config_waveunet3.json -- channels [32, 64, 96, 128], 5-tap convs, 4-tap stride-2
 conv_type 'gn', no attention, no noise-level embedding.  The chunk length is any positive multiple
 of 8 (three stride-2 levels).
 """
-import torch
 from torch import nn
+
+from ._facade import StrictFacade
 
 
 def _block(dim, dim_out, kernel_size, groups):
@@ -42,7 +43,10 @@ def _resample(channels, kernel_size, stride, transpose):
     return m
 
 
-class Waveunet3(nn.Module):
+class Waveunet3(StrictFacade):
+    """forward(x, y_t, noise_level): x (condition) and y_t [B, 1, N], N a positive multiple of 8;
+    noise_level [B] or [B, 1, 1] -> clamp(output_conv(...), -1, 1) [B, 1, N] (waveunet3.py:383-416, eval mode)."""
+
     hop_samples = 8                      # 2 ** (levels - 1): chunks are positive multiples of it
 
     def __init__(self, num_inputs, num_channels, downconv_kernel_size, upconv_kernel_size, bottleneck_kernel_size,
@@ -56,13 +60,13 @@ class Waveunet3(nn.Module):
             raise NotImplementedError
         if with_attn:
             raise NotImplementedError("Waveunet3 with self-attention (with_attn=True) has no HIP kernels")
-        self.config_args = {
+        self._init_facade({
             "num_inputs": num_inputs, "num_channels": list(num_channels), "downconv_kernel_size": downconv_kernel_size,
             "upconv_kernel_size": upconv_kernel_size, "bottleneck_kernel_size": bottleneck_kernel_size,
             "conv_stride": conv_stride, "conv_type": conv_type, "downsample_kernel_size": downsample_kernel_size,
             "upsample_kernel_size": upsample_kernel_size, "resample_stride": resample_stride,
             "with_noise_level_emb": bool(with_noise_level_emb), "norm_groups": norm_groups, "with_attn": bool(with_attn),
-            "dropout": dropout}
+            "dropout": dropout})
         C, n = list(num_channels), len(num_channels)
         self.noise_level_mlp = None
         w = nn.Module()
@@ -86,40 +90,3 @@ class Waveunet3(nn.Module):
         w.bottlenecks = nn.ModuleList([_resnet_block(C[-1], C[-1], bottleneck_kernel_size, norm_groups) for _ in range(2)])
         w.output_conv = nn.Conv1d(C[0], 1, 1)
         self.waveunet = w
-        self.num_samples = -1
-        self.compute_dtype = "float32"
-        self._ctx = None
-        self._ctx_key = None
-
-    def library_config(self):
-        return {"arch": {"type": "SDDM", "args": {}},
-                "diffusion": {"type": "GaussianDiffusion", "args": {"schedule": "linear", "n_timestep": 1}},
-                "network": {"type": "Waveunet3", "args": self.config_args}, "num_samples": -1}
-
-    def _context(self, device):
-        import sddm_hip
-        sd = dict(self.state_dict())
-        key = (device.index or 0, self.compute_dtype) + tuple((k, v.data_ptr(), v._version) for k, v in sd.items())
-        if self._ctx is None or self._ctx_key != key:
-            ctx = sddm_hip.Context(self.library_config(), device.index or 0, self.compute_dtype)
-            ctx.load_state_dict(sd)
-            self._ctx, self._ctx_key = ctx, key
-        return self._ctx
-
-    @torch.no_grad()
-    def forward(self, x, y_t, noise_level):
-        """x (condition) and y_t [B, 1, N], N a positive multiple of 8; noise_level [B] or [B, 1, 1]
-        -> clamp(output_conv(...), -1, 1) [B, 1, N] (waveunet3.py:383-416, eval mode)."""
-        if not y_t.is_cuda:
-            raise RuntimeError("Waveunet3 runs on the HIP device; move the tensors to cuda")
-        B = y_t.shape[0]
-        cond = x.reshape(B, 1, -1).contiguous().float()
-        yt = y_t.reshape(B, 1, -1).contiguous().float()
-        if cond.shape != yt.shape:
-            raise RuntimeError(f"condition {tuple(x.shape)} and y_t {tuple(y_t.shape)} differ in size")
-        nl = noise_level.reshape(-1).contiguous().float()
-        if nl.numel() != B:
-            raise RuntimeError(f"noise_level has {nl.numel()} elements for batch {B}")
-        out = torch.empty_like(yt)
-        self._context(yt.device).network_forward(cond, yt, nl, out)
-        return out

@@ -32,7 +32,7 @@ def main(out_path):
     sys.path.insert(0, os.path.join(os.path.dirname(HERE), "speech-denoising-diffusion-model-2_amd"))
     import torch
     import model.network as NW
-    import _waveunet_oracle as O
+    from _waveunet_film_oracle import WAVEUNET as O
     from _helpers import golden
     from _weights import make_params
 

@@ -27,7 +27,6 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 SCHED = ("linear", 3, 1e-4, 0.05)
-MODES = ("original", "condition_in", "sr3", "supportive", "conditional")
 DT_DIM2 = (1, 2, 3, 10, 17, 70)
 B, N = 2, 704
 
@@ -39,7 +38,7 @@ def main():
     args = ap.parse_args()
     for p in (HERE, os.path.join(REPO, "tests"), REPO):
         sys.path.insert(0, p)
-    from gen_golden import NoiseInjector
+    from gen_golden import INFER_CASES, load_seed0, record_infer
     from oracle import philox
     from _weights import make_params
     sys.path.insert(0, args.reference)
@@ -53,10 +52,7 @@ def main():
         cfg = json.load(f)
 
     def build(**change):
-        net = CAUNet(num_samples=N, **dict(cfg["network"]["args"], **change))
-        shapes = {k: tuple(v.shape) for k, v in net.state_dict().items()}
-        net.load_state_dict({k: torch.from_numpy(v) for k, v in make_params(shapes, 0).items()})
-        return net.eval(), shapes
+        return load_seed0(torch, make_params, CAUNet(num_samples=N, **dict(cfg["network"]["args"], **change)))
 
     net, shapes = build()
     n_par = sum(int(np.prod(s)) for s in shapes.values())
@@ -81,29 +77,8 @@ def main():
         out[f"dt/{d2}x8/x"], out[f"dt/{d2}x8/y"] = x, y
         print(f"Dual_Transformer {d2}x8: output rms {np.sqrt(np.mean(y ** 2)):.3f}", flush=True)
     out["inf/cond"] = cond
-    for nc, modes in (("sqrt_alpha_bar", MODES), ("time_step", ("original",))):
-        for mode in modes:
-            d = GaussianDiffusion(*SCHED, device="cpu")
-            m = SDDM(d, net, noise_condition=nc, p_transition=mode).eval()
-            steps = []
-
-            def rec(fn):
-                def w(*a, **kw):
-                    y = fn(*a, **kw)
-                    steps.append(y.numpy().copy())
-                    return y
-                return w
-            for fn in ("p_transition", "p_transition_sr3", "p_transition_supportive", "p_transition_conditional"):
-                setattr(d, fn, rec(getattr(d, fn)))
-            inj = NoiseInjector(torch, philox, 7)
-            inj.draws = ([] if mode == "supportive" else [0]) + list(range(SCHED[1], 1, -1))
-            with inj, torch.no_grad():
-                y = m.infer(torch.from_numpy(cond)).numpy().copy()
-            steps = np.stack(steps)
-            assert steps.shape == (SCHED[1], B, 1, N) and np.array_equal(steps[-1], y)
-            assert np.isfinite(steps).all()
-            print(f"{nc} {mode}: rms per step {['%.3f' % np.sqrt(np.mean(s ** 2)) for s in steps]}", flush=True)
-            out[f"inf/{nc}/{mode}/steps"] = steps
+    for nc, mode in INFER_CASES:
+        out[f"inf/{nc}/{mode}/steps"] = record_infer(torch, philox, GaussianDiffusion, SDDM, net, cond, SCHED, nc, mode)
     np.savez_compressed(os.path.join(args.out, "caunet.npz"), **out)
     with open(os.path.join(args.out, "caunet_keys.json"), "w") as f:
         json.dump([[k, list(s)] for k, s in shapes.items()], f, indent=0)

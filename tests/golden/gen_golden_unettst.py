@@ -26,7 +26,6 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 SCHED = ("linear", 3, 1e-4, 0.05)
-MODES = ("original", "condition_in", "sr3", "supportive", "conditional")
 DT_SHAPES = ((1, 4), (2, 4), (3, 4), (8, 4), (2, 8))
 B, N = 2, 4160
 
@@ -38,7 +37,7 @@ def main():
     args = ap.parse_args()
     for p in (HERE, os.path.join(REPO, "tests"), REPO):
         sys.path.insert(0, p)
-    from gen_golden import NoiseInjector
+    from gen_golden import INFER_CASES, load_seed0, record_infer
     from oracle import philox
     from _weights import make_params
     sys.path.insert(0, args.reference)
@@ -50,11 +49,7 @@ def main():
 
     with open(os.path.join(args.reference, "config_unettst.json")) as f:
         cfg = json.load(f)
-    net = UNetTST(num_samples=N, **cfg["network"]["args"])
-    shapes = {k: tuple(v.shape) for k, v in net.state_dict().items()}
-    P = make_params(shapes, 0)
-    net.load_state_dict({k: torch.from_numpy(v) for k, v in P.items()})
-    net.eval()
+    net, shapes = load_seed0(torch, make_params, UNetTST(num_samples=N, **cfg["network"]["args"]))
     n_par = sum(int(np.prod(s)) for s in shapes.values())
     assert len(shapes) == 454 and n_par == 8201395, (len(shapes), n_par)
     assert sum(int(np.prod(s)) for k, s in shapes.items() if k.startswith("mid.")) == 3438642
@@ -75,29 +70,8 @@ def main():
         out[f"dt/{d2}x{d1}/x"], out[f"dt/{d2}x{d1}/y"] = x, y
         print(f"Dual_Transformer {d2}x{d1}: output rms {np.sqrt(np.mean(y ** 2)):.3f}", flush=True)
     out["inf/cond"] = cond
-    for nc, modes in (("sqrt_alpha_bar", MODES), ("time_step", ("original",))):
-        for mode in modes:
-            d = GaussianDiffusion(*SCHED, device="cpu")
-            m = SDDM(d, net, noise_condition=nc, p_transition=mode).eval()
-            steps = []
-
-            def rec(fn):
-                def w(*a, **kw):
-                    y = fn(*a, **kw)
-                    steps.append(y.numpy().copy())
-                    return y
-                return w
-            for fn in ("p_transition", "p_transition_sr3", "p_transition_supportive", "p_transition_conditional"):
-                setattr(d, fn, rec(getattr(d, fn)))
-            inj = NoiseInjector(torch, philox, 7)
-            inj.draws = ([] if mode == "supportive" else [0]) + list(range(SCHED[1], 1, -1))
-            with inj, torch.no_grad():
-                y = m.infer(torch.from_numpy(cond)).numpy().copy()
-            steps = np.stack(steps)
-            assert steps.shape == (SCHED[1], B, 1, N) and np.array_equal(steps[-1], y)
-            assert np.isfinite(steps).all()
-            print(f"{nc} {mode}: rms per step {['%.3f' % np.sqrt(np.mean(s ** 2)) for s in steps]}", flush=True)
-            out[f"inf/{nc}/{mode}/steps"] = steps
+    for nc, mode in INFER_CASES:
+        out[f"inf/{nc}/{mode}/steps"] = record_infer(torch, philox, GaussianDiffusion, SDDM, net, cond, SCHED, nc, mode)
     np.savez_compressed(os.path.join(args.out, "unettst.npz"), **out)
     with open(os.path.join(args.out, "unettst_keys.json"), "w") as f:
         json.dump([[k, list(s)] for k, s in shapes.items()], f, indent=0)

@@ -25,12 +25,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 SCHED = ("linear", 3, 1e-4, 0.05)
-MODES = ("original", "condition_in", "sr3", "supportive", "conditional")
 B, N = 2, 296
-
-
-def clamped_share(x):
-    return float(np.mean(np.abs(x) >= 1.0))
 
 
 def main():
@@ -40,7 +35,7 @@ def main():
     args = ap.parse_args()
     for p in (HERE, os.path.join(REPO, "tests"), REPO):
         sys.path.insert(0, p)
-    from gen_golden import NoiseInjector
+    from gen_golden import CLAMP_CAPS, INFER_CASES, clamped_share, load_seed0, record_infer
     from oracle import philox
     from _weights import make_params
     sys.path.insert(0, args.reference)
@@ -52,11 +47,7 @@ def main():
 
     with open(os.path.join(args.reference, "config_waveunet2.json")) as f:
         cfg = json.load(f)
-    net = Waveunet2(**cfg["network"]["args"])
-    shapes = {k: tuple(v.shape) for k, v in net.state_dict().items()}
-    P = make_params(shapes, 0)
-    net.load_state_dict({k: torch.from_numpy(v) for k, v in P.items()})
-    net.eval()
+    net, shapes = load_seed0(torch, make_params, Waveunet2(**cfg["network"]["args"]))
     out = {}
     cond = np.clip(0.3 * philox.normal(5, 0, (B, 1, N)), -1, 1).astype(np.float32)
     x_t = philox.normal(6, 0, (B, 1, N))
@@ -71,35 +62,10 @@ def main():
     print(f"Waveunet2: {sum(int(np.prod(s)) for s in shapes.values())} parameters, {len(shapes)} keys, "
           f"eps rms {np.sqrt(np.mean(eps ** 2)):.3f}, clamped share {clamped_share(eps):.3f}", flush=True)
     out["inf/cond"] = cond
-    for nc, modes in (("sqrt_alpha_bar", MODES), ("time_step", ("original",))):
-        for mode in modes:
-            d = GaussianDiffusion(*SCHED, device="cpu")
-            m = SDDM(d, net, noise_condition=nc, p_transition=mode).eval()
-            steps = []
-
-            def rec(fn):
-                def w(*a, **kw):
-                    y = fn(*a, **kw)
-                    steps.append(y.numpy().copy())
-                    return y
-                return w
-            for fn in ("p_transition", "p_transition_sr3", "p_transition_supportive", "p_transition_conditional"):
-                setattr(d, fn, rec(getattr(d, fn)))
-            inj = NoiseInjector(torch, philox, 7)
-            inj.draws = ([] if mode == "supportive" else [0]) + list(range(SCHED[1], 1, -1))
-            with inj, torch.no_grad():
-                y = m.infer(torch.from_numpy(cond)).numpy().copy()
-            steps = np.stack(steps)
-            assert steps.shape == (SCHED[1], B, 1, N) and np.array_equal(steps[-1], y)
-            assert np.isfinite(steps).all()
-            shares = [clamped_share(s) for s in steps]
-            # at most 25 % of a final sample sits at +-1; the intermediates start from x_T ~ N(0, 1)
-            # (31.7 % beyond the clamp) and are held to 35 %, as in gen_golden_denoise_wavegrad.py
-            assert shares[-1] <= 0.25, f"{nc} {mode}: clamped share of the output {shares}"
-            assert max(shares) <= 0.35, f"{nc} {mode}: clamped share {shares}"
-            print(f"{nc} {mode}: clamped share per step {['%.3f' % s for s in shares]}", flush=True)
-            out[f"inf/{nc}/{mode}/out"] = y
-            out[f"inf/{nc}/{mode}/steps"] = steps
+    for nc, mode in INFER_CASES:
+        steps = record_infer(torch, philox, GaussianDiffusion, SDDM, net, cond, SCHED, nc, mode, caps=CLAMP_CAPS)
+        out[f"inf/{nc}/{mode}/out"] = steps[-1]
+        out[f"inf/{nc}/{mode}/steps"] = steps
     np.savez_compressed(os.path.join(args.out, "waveunet2.npz"), **out)
     with open(os.path.join(args.out, "waveunet2_keys.json"), "w") as f:
         json.dump([[k, list(s)] for k, s in shapes.items()], f, indent=0)

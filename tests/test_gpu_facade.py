@@ -146,3 +146,76 @@ def test_sddm_forward_training_step(torch_cuda, q_transition, noise_condition):
     assert rms(pred.cpu().numpy(), ref) <= 1e-4 * max(1.0, float(np.sqrt(np.mean(ref.astype(np.float64) ** 2))))
     with torch.no_grad(), pytest.raises(RuntimeError):
         m(tg(target).cpu(), tg(cond).cpu())
+
+
+# ---- the context cache every network facade shares (model/_facade.py)
+def _waveunet2_case():
+    import model.network as NW
+    from _waveunet_film_oracle import WAVEUNET2
+    rng = np.random.default_rng(51)
+    x, y_t = (rng.standard_normal((1, 1, 8)).astype(np.float32) for _ in range(2))
+    return (lambda: NW.Waveunet2(**WAVEUNET2.ARGS)), (x, y_t, np.array([0.6], np.float32))
+
+
+def _caunet_case():
+    import json
+    import os
+    import model
+    import model.network as NW
+    with open(os.path.join(os.path.dirname(os.path.dirname(model.__file__)), "configs", "config_caunet.json")) as f:
+        args = json.load(f)["network"]["args"]
+    rng = np.random.default_rng(52)
+    x, y_t = (rng.standard_normal((1, 1, 704)).astype(np.float32) for _ in range(2))
+    return (lambda: NW.CAUNet(num_samples=704, **args)), (x, y_t, np.array([0.6], np.float32))
+
+
+def _dual_transformer_case():
+    from model.CAUNet import Dual_Transformer
+    x = np.random.default_rng(53).standard_normal((1, 64, 1, 8)).astype(np.float32)
+    return (lambda: Dual_Transformer(64, 64, 0, 1)), (x,)
+
+
+@pytest.mark.parametrize("case", [_waveunet2_case, _caunet_case, _dual_transformer_case],
+                         ids=["strict-Waveunet2", "lenient-CAUNet", "mid-Dual_Transformer"])
+def test_context_cache_follows_weights_and_dtype(torch_cuda, case):
+    """The facades' _context: the same weights and dtype reuse the library context; a weight changed
+    in place, a load_state_dict (new versions) and another compute_dtype each build a new one, and the
+    new one holds the module's weights as they are then.  One case per family the shared base serves:
+    the strict forward, the lenient forward and the ``mid.``-prefixed load, at their smallest shapes."""
+    from _weights import make_params
+    build, inputs = case()
+    inputs = [torch.from_numpy(a).cuda() for a in inputs]
+
+    def fresh(weights):
+        n = build()
+        n.load_state_dict(weights)
+        return n.cuda()
+    n = build()
+    P = make_params({k: tuple(v.shape) for k, v in n.state_dict().items()}, 0)
+    original = {k: torch.from_numpy(v) for k, v in P.items()}
+    n = fresh(original)
+    # 1. the same inputs twice: one context, the same bits
+    out1 = n(*inputs).cpu().numpy()
+    ctx1 = n._ctx
+    assert ctx1 is not None and np.isfinite(out1).all()
+    assert np.array_equal(n(*inputs).cpu().numpy(), out1) and n._ctx is ctx1
+    # 2. one weight tensor changed in place: a new context with the changed weights
+    with torch.no_grad():
+        next(iter(n.parameters())).mul_(1.5)
+    out2 = n(*inputs).cpu().numpy()
+    ctx2 = n._ctx
+    assert ctx2 is not ctx1
+    assert not np.array_equal(out2, out1)
+    changed = {k: v.detach().cpu().clone() for k, v in n.state_dict().items()}
+    assert np.array_equal(fresh(changed)(*inputs).cpu().numpy(), out2)
+    # 3. the original weights loaded again: new versions, a new context, the bits of step 1
+    n.load_state_dict(original)
+    out3 = n(*inputs).cpu().numpy()
+    ctx3 = n._ctx
+    assert ctx3 is not ctx2 and ctx3 is not ctx1
+    assert np.array_equal(out3, out1)
+    # 4. another compute dtype: a new context
+    n.compute_dtype = "bfloat16"
+    ctx4 = n._context(inputs[0].device)
+    assert ctx4 is not ctx3 and n._ctx is ctx4
+    assert n._context(inputs[0].device) is ctx4

@@ -50,9 +50,8 @@ import numpy as np
 import pytest
 
 import _denoise_wavegrad_oracle as DO
-import _waveunet2_oracle as W2O
-import _waveunet_oracle as W1O
 import _waveunet3_oracle as WO
+from _waveunet_film_oracle import WAVEUNET as W1O, WAVEUNET2 as W2O
 from _helpers import GOLDEN, diffwave_params, wavegrad_params
 from _weights import make_params
 

@@ -34,7 +34,7 @@ import numpy as np
 import pytest
 import torch
 
-import _waveunet_oracle as O
+from _waveunet_film_oracle import WAVEUNET as O
 import _wu_paths_child as child
 from _helpers import golden, rms
 from _weights import make_params

@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 import torch
 
-import _waveunet2_oracle as O
+from _waveunet_film_oracle import WAVEUNET2 as O
 from _helpers import golden, rms
 from _weights import make_params
 

@@ -25,7 +25,7 @@ def _model():
     import model.diffusion as D
     import model.model as M
     import model.network as NW
-    import _waveunet_oracle as O
+    from _waveunet_film_oracle import WAVEUNET as O
     from _weights import make_params
     dev = torch.device("cuda", 0)
     net = NW.Waveunet(**O.ARGS)

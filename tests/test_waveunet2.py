@@ -89,7 +89,7 @@ def test_facade_needs_the_hip_device():
 
 def test_oracle_matches_reference_forward():
     """Pins the torch restatement that the larger GPU cases are checked against."""
-    import _waveunet2_oracle as O
+    from _waveunet_film_oracle import WAVEUNET2 as O
     shapes = O.param_shapes()
     assert [[k, list(s)] for k, s in sorted(shapes.items())] == sorted(_keys())
     assert O.ARGS == _reference_config()["network"]["args"]
@@ -108,7 +108,7 @@ def test_oracle_matches_reference_forward():
 def test_oracle_sampling_matches_reference(nc, mode):
     """The oracle looped by the oracle sampler against the reference's unmodified SDDM.infer: the
     output and every intermediate x_t."""
-    import _waveunet2_oracle as O
+    from _waveunet_film_oracle import WAVEUNET2 as O
     from oracle import sampler
     z = golden("waveunet2.npz")
     P = make_params(O.param_shapes(), 0)
