@@ -77,33 +77,9 @@ static std::map<std::string, std::vector<int64_t>> cau_param_shapes(const CAUSta
       s[p + "upsample.2.weight"] = {64};
     }
   }
-  const int64_t C = kCauC, dm = kCauD;
-  s["mid.input.0.weight"] = {dm, C, 1, 1}; s["mid.input.0.bias"] = {dm}; s["mid.input.1.weight"] = {dm};
-  s["mid.output.0.weight"] = {C, dm, 1, 1}; s["mid.output.0.bias"] = {C}; s["mid.output.1.weight"] = {C};
-  for (int i = 0; i < d.n_tstb; ++i)
-    for (const char* pass : {"row", "col"}) {
-      const std::string e = std::string("mid.") + pass + "_trans." + std::to_string(i);
-      s[e + ".self_attn.in_proj_weight"] = {3 * dm, dm}; s[e + ".self_attn.in_proj_bias"] = {3 * dm};
-      s[e + ".self_attn.out_proj.weight"] = {dm, dm}; s[e + ".self_attn.out_proj.bias"] = {dm};
-      for (const char* sfx : {"", "_reverse"}) {
-        s[e + ".gru.weight_ih_l0" + sfx] = {6 * dm, dm}; s[e + ".gru.weight_hh_l0" + sfx] = {6 * dm, 2 * dm};
-        s[e + ".gru.bias_ih_l0" + sfx] = {6 * dm}; s[e + ".gru.bias_hh_l0" + sfx] = {6 * dm};
-      }
-      s[e + ".linear2.weight"] = {dm, 4 * dm}; s[e + ".linear2.bias"] = {dm};
-      for (const char* nm : {".norm1", ".norm2"}) { s[e + nm + ".weight"] = {dm}; s[e + nm + ".bias"] = {dm}; }
-      const std::string gn = std::string("mid.") + pass + "_norm." + std::to_string(i);
-      s[gn + ".weight"] = {dm}; s[gn + ".bias"] = {dm};
-    }
+  dt_param_shapes(s, "mid", kCauC, d.n_tstb, true);       // CAUNet.py:152-178: one PReLU slope per channel
   s["final_conv.weight"] = {1, 64, 1, 1}; s["final_conv.bias"] = {1};
   return s;
-}
-
-// W[n][k] (row-major, K a multiple of 32) -> MFMA A fragments [N / 16][K / 32][64 lanes][8] at element `off` of `dst`
-static void cau_store_frags(char* dst, size_t off, const float* w, int N, int K, int dt) {
-  const int KC = K / 32;
-  for (int o = 0; o < N; ++o)
-    for (int k = 0; k < K; ++k)
-      store_elem(dst, off + ((size_t)((o / 16) * KC + k / 32) * 64 + (o % 16) + 16 * ((k % 32) / 8)) * 8 + k % 8, w[(size_t)o * K + k], dt);
 }
 
 // conv weight [co][ci][KH][3] (ci = nsrc * 64) -> fragments of W[co][k], k = ((s KH + kh) 3 + kw) 64 + c
@@ -116,12 +92,11 @@ static void cau_add_conv(sddm_ctx* c, WeightPacker& pk, const std::string& name,
         for (int kw = 0; kw < 3; ++kw)
           for (int ch = 0; ch < 64; ++ch)
             m[(size_t)o * K + ((s * KH + kh) * 3 + kw) * 64 + ch] = w[(((size_t)o * ci + s * 64 + ch) * KH + kh) * 3 + kw];
-  cau_store_frags(pk.raw(name, m.size() * dtype_size(c->dtype)), 0, m.data(), co, K, c->dtype);
+  store_frags(pk.raw(name, m.size() * dtype_size(c->dtype)), 0, m.data(), co, K, c->dtype);
 }
 
 size_t CAUState::pack(sddm_ctx* c, WeightPacker& pk) {
   auto P = [&](const std::string& k) -> const std::vector<float>& { return c->params.at(k).data; };
-  const int dt = c->dtype;
   pk.f32("first.w", P("first_conv.weight"));
   pk.f32("first.b", P("first_conv.bias"));
   std::vector<float> w1, b1, a1, w2, b2;               // the eight noise MLPs, layer-major
@@ -148,40 +123,7 @@ size_t CAUState::pack(sddm_ctx* c, WeightPacker& pk) {
     cat(w2, P(p + "noise_func.noise_func.2.weight")); cat(b2, P(p + "noise_func.noise_func.2.bias"));
   }
   pk.f32("mlp.w1", w1); pk.f32("mlp.b1", b1); pk.f32("mlp.a1", a1); pk.f32("mlp.w2", w2); pk.f32("mlp.b2", b2);
-  {  // Dual_Transformer: matrices as fragments in the compute dtype, vectors fp32, at the offsets of caunet.h
-    const int ne = 2 * n_tstb;
-    char* wm = pk.raw("mid.wmat", ((size_t)kCauWEnc0 + (size_t)ne * kCauEncW) * dtype_size(dt));
-    std::vector<float> wv((size_t)kCauVEnc0 + (size_t)ne * kCauEncV, 0.f);
-    auto frag = [&](size_t off, const std::vector<float>& w, int N, int K) { cau_store_frags(wm, off, w.data(), N, K, dt); };
-    auto vec = [&](size_t off, const std::vector<float>& v) { std::copy(v.begin(), v.end(), wv.begin() + off); };
-    frag(kCauWIn, P("mid.input.0.weight"), kCauD, kCauC);
-    frag(kCauWOut, P("mid.output.0.weight"), kCauC, kCauD);
-    vec(kCauVInB, P("mid.input.0.bias")); vec(kCauVInA, P("mid.input.1.weight"));
-    vec(kCauVOutB, P("mid.output.0.bias")); vec(kCauVOutA, P("mid.output.1.weight"));
-    for (int e = 0; e < ne; ++e) {
-      const char* pass = e % 2 ? "col" : "row";
-      const std::string p = std::string("mid.") + pass + "_trans." + std::to_string(e / 2);
-      const std::string gn = std::string("mid.") + pass + "_norm." + std::to_string(e / 2);
-      const size_t wo = (size_t)kCauWEnc0 + (size_t)e * kCauEncW, vo = (size_t)kCauVEnc0 + (size_t)e * kCauEncV;
-      frag(wo + kCauEInProj, P(p + ".self_attn.in_proj_weight"), 3 * kCauD, kCauD);
-      frag(wo + kCauEOutProj, P(p + ".self_attn.out_proj.weight"), kCauD, kCauD);
-      for (int d = 0; d < 2; ++d) {
-        const std::string sfx = d ? "_reverse" : "";
-        frag(wo + kCauEIh + (size_t)d * kCauEIhSize, P(p + ".gru.weight_ih_l0" + sfx), 3 * kCauHid, kCauD);
-        frag(wo + kCauEHh + (size_t)d * kCauEHhSize, P(p + ".gru.weight_hh_l0" + sfx), 3 * kCauHid, kCauHid);
-        vec(vo + kCauVBih + 384 * d, P(p + ".gru.bias_ih_l0" + sfx));
-        vec(vo + kCauVBhh + 384 * d, P(p + ".gru.bias_hh_l0" + sfx));
-      }
-      frag(wo + kCauELin2, P(p + ".linear2.weight"), kCauD, 2 * kCauHid);
-      vec(vo + kCauVInProjB, P(p + ".self_attn.in_proj_bias"));
-      vec(vo + kCauVOutProjB, P(p + ".self_attn.out_proj.bias"));
-      vec(vo + kCauVLn1W, P(p + ".norm1.weight")); vec(vo + kCauVLn1B, P(p + ".norm1.bias"));
-      vec(vo + kCauVLin2B, P(p + ".linear2.bias"));
-      vec(vo + kCauVLn2W, P(p + ".norm2.weight")); vec(vo + kCauVLn2B, P(p + ".norm2.bias"));
-      vec(vo + kCauVGnW, P(gn + ".weight")); vec(vo + kCauVGnB, P(gn + ".bias"));
-    }
-    pk.f32("mid.wvec", wv);
-  }
+  dt_pack(c, pk, "mid", kCauLayout, n_tstb);           // at the offsets of caunet.h
   pk.f32("final.w", P("final_conv.weight"));
   pk.f32("final.b", P("final_conv.bias"));
   return 0;                                            // no table of its own: the level is one scalar per t

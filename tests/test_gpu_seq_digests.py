@@ -40,6 +40,13 @@ bfloat16, fw and sample under time_step and in float16, and one forward-only kin
 three dtypes:
   odd      network_forward at B = 3, N = 6144 (96 ... 3): no powers of two, partly filled tiles, an
            odd batch
+The CAUNet entries were recorded before the UNet runtime moved into unet_runtime.h and CAUNet's
+Dual_Transformer packer was shared with UNetTST's; that recording reproduced the first 131.  CAUNet
+(_caunet_oracle.ARGS) frames 128 samples every 64: its N is 704 (10 frames, more than the widest dense
+dilation), its reshape length 320.  It runs the five kinds in float32 and bfloat16, fw and sample in
+float16, and one kind of its own in float32 and bfloat16:
+  dt       dual_transformer on [2, 64, 17, 8], on a context of its own where only mid.* is loaded
+           (every other parameter packs as zeros)
 """
 import functools
 import hashlib
@@ -49,6 +56,7 @@ import os
 import numpy as np
 import pytest
 
+import _caunet_oracle as CO
 import _denoise_wavegrad_oracle as DO
 import _waveunet3_oracle as WO
 from _waveunet_film_oracle import WAVEUNET as W1O, WAVEUNET2 as W2O
@@ -87,6 +95,12 @@ CASES += [f"Waveunet/{d}/{k}" for d in ("float32", "bfloat16") for k in KINDS]
 CASES += [f"Waveunet-time_step/{d}/{k}" for d in ("float32", "bfloat16") for k in ("fw", "sample")]
 CASES += [f"Waveunet/float16/{k}" for k in ("fw", "sample")]
 CASES += [f"Waveunet/{d}/{k}" for d in ("float32", "bfloat16", "float16") for k in SHAPES12]
+# CAUNet, appended behind the first 131
+NETS["CAUNet"] = ("CAUNet", 704, 320, 0, 1, "sqrt_alpha_bar")
+NET_ARGS["CAUNet"] = CO.ARGS
+CASES += [f"CAUNet/{d}/{k}" for d in ("float32", "bfloat16") for k in KINDS]
+CASES += [f"CAUNet/float16/{k}" for k in ("fw", "sample")]
+CASES += [f"CAUNet/{d}/dt" for d in ("float32", "bfloat16")]
 
 _CTX = {}
 
@@ -103,11 +117,14 @@ def _params(net_type):
         return make_params(W2O.param_shapes(), 0)
     if net_type == "Waveunet":
         return make_params(W1O.param_shapes(), 0)
+    if net_type == "CAUNet":
+        return make_params(CO.param_shapes(), 0)
     return make_params(DO.param_shapes(net_type), 0)
 
 
-def _ctx(net, dtype):
-    if (net, dtype) not in _CTX:
+def _ctx(net, dtype, only=None):
+    """The context of (net, dtype); `only`: a context of its own with just that prefix's parameters."""
+    if only is not None or (net, dtype) not in _CTX:
         import sddm_hip
         net_type, _, _, bins, hop, nc = NETS[net]
         if bins:
@@ -121,6 +138,10 @@ def _ctx(net, dtype):
                "network": {"type": net_type, "args": dict(NET_ARGS.get(net_type, {}))},
                "num_samples": -1}
         ctx = sddm_hip.Context(cfg, 0, dtype)
+        if only is not None:
+            ctx.load_state_dict({k: v for k, v in _params(net_type).items() if k.startswith(only)})
+            assert ctx.missing() > 0
+            return ctx
         ctx.load_state_dict(_params(net_type))
         assert ctx.missing() == 0
         _CTX[net, dtype] = ctx
@@ -158,8 +179,14 @@ def run_case(torch, case):
     """The output array of one case (fp32 on the host)."""
     net, dtype, kind = case.split("/")
     N, N2 = NETS[net][1:3]
-    ctx = _ctx(net, dtype)
     dev = torch.device("cuda", 0)
+    if kind == "dt":
+        x = np.random.default_rng(17).standard_normal((2, 64, 17, 8)).astype(np.float32)
+        y = torch.full(x.shape, float("nan"), device=dev)
+        _ctx(net, dtype, only="mid.").dual_transformer(torch.from_numpy(x).to(dev), y)
+        torch.cuda.synchronize()
+        return y.cpu().numpy()
+    ctx = _ctx(net, dtype)
     if kind == "fw":
         return _forward(torch, ctx, net, B, N, 5)
     if kind in ALL_SHAPES:

@@ -16,6 +16,21 @@ well under a second on an MI355X):
   fw16448/<dtype>/<table>       B=16 x N=16448 on the forced tables and on the repository's measured
                                  table: every compile-time-shape kernel
   sample2112/bfloat16/graph4    4 graph-replayed sampling steps, B=2 x N=2112
+
+The cases below were appended (and recorded with the parent's library; that recording reproduced the
+22 above) before the UNet runtime moved out of sddm_runtime.cpp into unet_runtime.h: the branches of
+the lane path and the UNetTST plan that the first 22 do not reach.  N = 2112 (every level down to
+1 x 4), T = 4 where sampling:
+  sample2112/bfloat16/record    sample_continuous, sample_inter 2, B=2: out, then the two recorded
+                                 states (the per-launch loop, no graph)
+  sample2112/float32/noise      sample_noise with seeded draws [5][2][1][2112] (per-launch as well)
+  sample2112/bfloat16/lanes     B=5 under "lane_rows": 2: three lanes, the last one partial, on three
+                                 streams, graph replay (SDDM_LANE_ROWS unset)
+  tst2112/<dtype>/fw            UNetTST (_unettst_oracle.ARGS), forward at B=2
+  tst2112/bfloat16/graph4       UNetTST, 4 graph-replayed sampling steps, B=2
+  tst2112/float32/res2          UNetTST forward with res_blocks 2: the concatenation step of the plan
+  tst/<dtype>/dt                Context.dual_transformer on [2, 160, 2, 4] where only mid.* is loaded
+                                 (every other parameter packs as zeros)
 """
 import hashlib
 import json
@@ -24,8 +39,10 @@ import os
 import numpy as np
 import pytest
 
+import _unettst_oracle as TO
 import test_gpu_unet as tu
-from _helpers import GOLDEN, golden
+from _helpers import GOLDEN, golden, unet_config
+from _weights import make_params
 
 pytestmark = pytest.mark.gpu
 
@@ -42,7 +59,13 @@ CASES = (
                                       ("bfloat16", "chain"), ("float16", "chain"), ("bfloat16", "repo"),
                                       ("float16", "repo"))]
     + ["sample2112/bfloat16/graph4"]
+    # appended behind the first 22, whose names and order stay
+    + ["sample2112/bfloat16/record", "sample2112/float32/noise", "sample2112/bfloat16/lanes"]
+    + [f"tst2112/{d}/fw" for d in ("float32", "bfloat16", "float16")]
+    + ["tst2112/bfloat16/graph4", "tst2112/float32/res2"]
+    + [f"tst/{d}/dt" for d in ("float32", "bfloat16")]
 )
+SCHED4 = ("linear", 4, 1e-6, 1e-3)
 
 _INPUTS = {}
 
@@ -68,14 +91,63 @@ def digest(a):
     return hashlib.sha256(a.tobytes()).hexdigest()
 
 
+def _tst_ctx(dtype, sched=("linear", 100, 1e-6, 1e-3), only=None, lane_rows=None, **change):
+    """A UNetTST context at N = 2112; `only`: load just the parameters with that prefix."""
+    import sddm_hip
+    args = dict(TO.ARGS, **change)
+    cfg = unet_config(2112, sched)
+    cfg["network"] = {"type": "UNetTST", "args": args}
+    ctx = sddm_hip.Context(cfg, 0, dtype)
+    P = make_params(TO.param_shapes(args), 0)
+    ctx.load_state_dict({k: v for k, v in P.items() if only is None or k.startswith(only)})
+    assert (ctx.missing() == 0) == (only is None)
+    return ctx
+
+
+def _sample_case(torch, ctx, what):
+    """sampling at N = 2112, T = 4: graph4 and lanes replay graphs, record and noise launch per step."""
+    from sddm_hip.synth import noisy_speech
+    dev = torch.device("cuda", 0)
+    rows = 5 if what == "lanes" else 2
+    cond_np = noisy_speech(rows, 2112, seed=99)
+    if what in ("graph4", "lanes"):
+        return tu._sample(torch, ctx, cond_np)
+    cond = torch.from_numpy(cond_np).to(dev)
+    out = torch.full_like(cond, float("nan"))
+    if what == "record":
+        record = torch.full((2,) + tuple(cond.shape), float("nan"), device=dev)
+        ctx.sample_continuous(cond, out, record, 2, 7, 0)
+        out = torch.cat([out[None], record])
+    else:
+        draws = np.random.default_rng(11).standard_normal((5, 2, 1, 2112)).astype(np.float32)
+        ctx.sample_noise(cond, out, torch.from_numpy(draws).to(dev))
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
 def run_case(torch, case):
     """The output array of one case (fp32 on the host)."""
     shape, dtype, what = case.split("/")
     dev = torch.device("cuda", 0)
     if shape == "sample2112":
-        from sddm_hip.synth import noisy_speech
-        ctx = tu.make_ctx(2112, dtype, ("linear", 4, 1e-6, 1e-3))
-        return tu._sample(torch, ctx, noisy_speech(2, 2112, seed=99))
+        if what != "lanes":
+            return _sample_case(torch, tu.make_ctx(2112, dtype, SCHED4), what)
+        import sddm_hip
+        assert "SDDM_LANE_ROWS" not in os.environ, "SDDM_LANE_ROWS overrides the config's lane_rows"
+        ctx = sddm_hip.Context(dict(unet_config(2112, SCHED4), lane_rows=2), 0, dtype)
+        ctx.load_state_dict(tu.unet_params(2112))
+        return _sample_case(torch, ctx, what)
+    if shape == "tst":
+        x = np.random.default_rng(17).standard_normal((2, 160, 2, 4)).astype(np.float32)
+        y = torch.full(x.shape, float("nan"), device=dev)
+        _tst_ctx(dtype, only="mid.").dual_transformer(torch.from_numpy(x).to(dev), y)
+        torch.cuda.synchronize()
+        return y.cpu().numpy()
+    if shape == "tst2112":
+        if what == "graph4":
+            return _sample_case(torch, _tst_ctx(dtype, SCHED4), what)
+        ctx = _tst_ctx(dtype, res_blocks=2) if what == "res2" else _tst_ctx(dtype)
+        return tu._forward(torch, ctx, golden("unet_forward.npz"), 2112)
     N = int(shape[2:])
     ctx = tu.make_ctx(N, dtype)
     if what == "repo":
