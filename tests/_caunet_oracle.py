@@ -19,6 +19,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import _dual_transformer_oracle as DT
+
 ARGS = {"inner_channel": 64, "n_encode_layers": 4, "dense_depth": 3, "n_TSTB": 6, "segment_len": 128,
         "segment_stride": 64, "use_affine_level": False}
 
@@ -34,22 +36,7 @@ def _widths(args):
 
 
 def dual_transformer_shapes(C=64, n_tstb=6, prefix="mid."):
-    d, s = C // 2, {}
-    s[prefix + "input.0.weight"], s[prefix + "input.0.bias"], s[prefix + "input.1.weight"] = (d, C, 1, 1), (d,), (d,)
-    for i in range(n_tstb):
-        for p in ("row", "col"):
-            e = f"{prefix}{p}_trans.{i}."
-            s[e + "self_attn.in_proj_weight"], s[e + "self_attn.in_proj_bias"] = (3 * d, d), (3 * d,)
-            s[e + "self_attn.out_proj.weight"], s[e + "self_attn.out_proj.bias"] = (d, d), (d,)
-            for sfx in ("", "_reverse"):
-                s[e + "gru.weight_ih_l0" + sfx], s[e + "gru.weight_hh_l0" + sfx] = (6 * d, d), (6 * d, 2 * d)
-                s[e + "gru.bias_ih_l0" + sfx], s[e + "gru.bias_hh_l0" + sfx] = (6 * d,), (6 * d,)
-            s[e + "linear2.weight"], s[e + "linear2.bias"] = (d, 4 * d), (d,)
-            for n in ("norm1", "norm2"):
-                s[e + n + ".weight"], s[e + n + ".bias"] = (d,), (d,)
-            s[f"{prefix}{p}_norm.{i}.weight"], s[f"{prefix}{p}_norm.{i}.bias"] = (d,), (d,)
-    s[prefix + "output.0.weight"], s[prefix + "output.0.bias"], s[prefix + "output.1.weight"] = (C, d, 1, 1), (C,), (C,)
-    return s
+    return DT.shapes(C, n_tstb, prefix, per_channel=True)
 
 
 def param_shapes(args=None):
@@ -79,58 +66,11 @@ def param_shapes(args=None):
     return s
 
 
-def _q(rounding):
-    return (lambda t: t) if rounding is None else (lambda t: t.to(rounding).to(torch.float64))
-
-
-def _w64(P):
-    return {k: torch.from_numpy(np.asarray(v, np.float64)) for k, v in P.items()}
-
-
-def _encoder(W, e, x, q):
-    """One TransformerEncoderLayer: x [L, Nb, d] -> [L, Nb, d]; 4 heads, GRU hidden 2 d per direction."""
-    L, Nb, d = x.shape
-    H, hd = 4, d // 4
-    qkv = q(x) @ q(W[e + "self_attn.in_proj_weight"]).T + W[e + "self_attn.in_proj_bias"]
-    qh, kh, vh = (t.reshape(L, Nb * H, hd).transpose(0, 1) for t in qkv.chunk(3, dim=-1))
-    a = q(torch.softmax(q(qh * hd ** -0.5) @ q(kh).transpose(1, 2), dim=-1)) @ q(vh)     # [Nb * H, L, hd]
-    a = a.transpose(0, 1).reshape(L, Nb, d)
-    a = q(a) @ q(W[e + "self_attn.out_proj.weight"]).T + W[e + "self_attn.out_proj.bias"]
-    src = F.layer_norm(x + a, (d,), W[e + "norm1.weight"], W[e + "norm1.bias"], 1e-5)
-    outs = []
-    for sfx, order in (("", range(L)), ("_reverse", range(L - 1, -1, -1))):             # gates r, z, n; h0 = 0
-        wih, whh = q(W[e + "gru.weight_ih_l0" + sfx]), q(W[e + "gru.weight_hh_l0" + sfx])
-        bih, bhh = W[e + "gru.bias_ih_l0" + sfx], W[e + "gru.bias_hh_l0" + sfx]
-        gi_all = q(src) @ wih.T + bih
-        h = torch.zeros(Nb, 2 * d, dtype=torch.float64)
-        o = [None] * L
-        for t in order:
-            gi, gh = gi_all[t].chunk(3, -1), (q(h) @ whh.T + bhh).chunk(3, -1)
-            r, z = torch.sigmoid(gi[0] + gh[0]), torch.sigmoid(gi[1] + gh[1])
-            n = torch.tanh(gi[2] + r * gh[2])
-            h = (1 - z) * n + z * h
-            o[t] = h
-        outs.append(torch.stack(o))
-    out = torch.cat(outs, dim=-1)
-    s2 = q(F.relu(out)) @ q(W[e + "linear2.weight"]).T + W[e + "linear2.bias"]
-    return F.layer_norm(src + s2, (d,), W[e + "norm2.weight"], W[e + "norm2.bias"], 1e-5)
+_q, _w64 = DT.rounder, DT.w64
 
 
 def _dual_transformer(W, x, q, n_tstb, prefix="mid."):
-    """The block on float64 [b, C, dim2, dim1]: per-channel PReLUs, GroupNorm(1, C / 2, eps 1e-8)."""
-    b, C, dim2, dim1 = x.shape
-    d = C // 2
-    out = F.conv2d(q(x), q(W[prefix + "input.0.weight"]), W[prefix + "input.0.bias"])
-    out = F.prelu(out, W[prefix + "input.1.weight"])
-    for i in range(n_tstb):
-        row = out.permute(3, 0, 2, 1).reshape(dim1, b * dim2, d)
-        row = _encoder(W, f"{prefix}row_trans.{i}.", row, q).reshape(dim1, b, dim2, d).permute(1, 3, 2, 0)
-        out = out + F.group_norm(row, 1, W[f"{prefix}row_norm.{i}.weight"], W[f"{prefix}row_norm.{i}.bias"], 1e-8)
-        col = out.permute(2, 0, 3, 1).reshape(dim2, b * dim1, d)
-        col = _encoder(W, f"{prefix}col_trans.{i}.", col, q).reshape(dim2, b, dim1, d).permute(1, 3, 0, 2)
-        out = out + F.group_norm(col, 1, W[f"{prefix}col_norm.{i}.weight"], W[f"{prefix}col_norm.{i}.bias"], 1e-8)
-    out = F.conv2d(q(out), q(W[prefix + "output.0.weight"]), W[prefix + "output.0.bias"])
-    return q(F.prelu(out, W[prefix + "output.1.weight"]))
+    return DT.block(W, x, q, n_tstb, prefix, round_attention=True, hoist_gru=True)
 
 
 def dual_transformer(P, x, rounding=None, n_tstb=6, prefix="mid."):

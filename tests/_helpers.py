@@ -1,6 +1,8 @@
 """Shared test helpers: fixtures, configs and deterministic weights (test infrastructure)."""
 import copy
 import os
+import socket
+import struct
 
 import numpy as np
 
@@ -69,3 +71,21 @@ def wavegrad_params(seed=0):
     """Deterministic WaveGrad weights with the reference key names (no module prefix)."""
     from oracle.wavegrad import param_shapes
     return make_params(param_shapes(), seed)
+
+
+def write_pcm16(path, x, sr=16000):
+    """A mono 16-bit PCM WAV of x in [-1, 1)."""
+    pcm = np.clip(np.round(x * 32768), -32768, 32767).astype("<i2").tobytes()
+    hdr = struct.pack("<4sI4s4sIHHIIHH4sI", b"RIFF", 36 + len(pcm), b"WAVE", b"fmt ", 16, 1, 1, sr, 2 * sr, 2, 16,
+                      b"data", len(pcm))
+    with open(path, "wb") as f:
+        f.write(hdr + pcm)
+
+
+def free_port():
+    """A TCP port that was free a moment ago, for a process group's MASTER_PORT."""
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    return port

@@ -26,9 +26,7 @@ unless noted):
   rows, row shards, two ranks                        bit-equal
 """
 import functools
-import json
 import os
-import struct
 import sys
 
 import numpy as np
@@ -36,6 +34,7 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+import _net_suite as S
 import _caunet_oracle as O
 from _helpers import golden, rms
 from _weights import make_params
@@ -43,69 +42,25 @@ from _weights import make_params
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SCHED = ("linear", 3, 1e-4, 0.05)
-MODES = ("original", "condition_in", "sr3", "supportive", "conditional")
 DT_DIM2 = (1, 2, 3, 10, 17, 70)
 DTYPES = ("float32", "bfloat16", "float16")
-_NETS = {}
+CASE = S.NetCase("CAUNet", O, "caunet.npz", 704, dual_transformer=True, rounding=True, emulated_bar16=True,
+                 state_dict_count=450, loads_state_dict=False, refusal_match=True, gated_sampling_bar=True,
+                 sharded_infer=True, cli_config="config_caunet.json", cli_chunk=704, cli_lengths=(1800, 500),
+                 cli_num_samples=("==", 16448), cli_exact_shape=False)
+_inputs, _gate, _bar16, _run = S.inputs, S.gate, S.bar16, S.run
 
 
-def _args(**change):
-    return dict(O.ARGS, **change)
-
-
-@functools.lru_cache(maxsize=None)
 def _params(n_tstb=6, affine=False):
-    return make_params(O.param_shapes(_args(n_TSTB=n_tstb, use_affine_level=affine)), 0)
+    return S.params(CASE, n_TSTB=n_tstb, use_affine_level=affine)
 
 
 def _net(N, dtype="float32", n_tstb=6, affine=False):
-    """One facade network per (length, dtype, variant), shared by the tests (its weights never change)."""
-    key = (N, dtype, n_tstb, affine)
-    if key not in _NETS:
-        import model.network as NW
-        n = NW.CAUNet(num_samples=N, **_args(n_TSTB=n_tstb, use_affine_level=affine))
-        n.load_state_dict({k: torch.from_numpy(v) for k, v in _params(n_tstb, affine).items()})
-        n.compute_dtype = dtype
-        n.mid.compute_dtype = dtype
-        _NETS[key] = n.cuda()
-    return _NETS[key]
+    return S.net(CASE, N, dtype, n_TSTB=n_tstb, use_affine_level=affine)
 
 
-def _model(N, mode="original", noise_condition="sqrt_alpha_bar", dtype="float32"):
-    import model.diffusion as D
-    import model.model as M
-    d = D.GaussianDiffusion(*SCHED, device="cuda")
-    return M.SDDM(d, _net(N, dtype), noise_condition=noise_condition, p_transition=mode, compute_dtype=dtype).cuda()
-
-
-def _inputs(B, N, seed):
-    rng = np.random.default_rng(seed)
-    cond = np.clip(0.3 * rng.standard_normal((B, 1, N)), -1, 1).astype(np.float32)
-    x_t = rng.standard_normal((B, 1, N)).astype(np.float32)
-    nl = rng.uniform(0.05, 0.99, B).astype(np.float32)
-    return cond, x_t, nl
-
-
-def _gate(ref):
-    return max(1.0, rms(ref, 0))
-
-
-def _bar16(dtype, emu):
-    """The 16-bit bar: the project's where the CPU emulation's error is at most half of it, else twice
-    the emulation's."""
-    project = {"bfloat16": 3e-2, "float16": 5e-3}[dtype]
-    return project if emu <= 0.5 * project else 2.0 * emu
-
-
-def _run(net, cond, x_t, nl):
-    return net(torch.from_numpy(cond).cuda(), torch.from_numpy(x_t).cuda(), torch.from_numpy(nl).cuda()).cpu().numpy()
-
-
-@functools.lru_cache(maxsize=None)
 def _oracle_case(B, N, n_tstb=6):
-    cond, x_t, nl = _inputs(B, N, seed=31)
-    return cond, x_t, nl, O.forward(_params(n_tstb), cond, x_t, nl, args=_args(n_TSTB=n_tstb))
+    return S.oracle_case(CASE, B, N, n_TSTB=n_tstb)
 
 
 @functools.lru_cache(maxsize=None)
@@ -225,39 +180,13 @@ def test_rows_are_independent_of_the_batch(torch_cuda, dtype):
 
 
 # ---- 13: sampling
-@pytest.mark.parametrize("nc,mode", [("sqrt_alpha_bar", m) for m in MODES] + [("time_step", "original")])
+@pytest.mark.parametrize("nc,mode", S.SAMPLING_CASES)
 def test_sampling_matches_reference(torch_cuda, nc, mode):
-    """The reference's unmodified SDDM.infer: the output and every intermediate x_t; a second run is
-    bit-equal."""
-    z = golden("caunet.npz")
-    steps = z[f"inf/{nc}/{mode}/steps"]
-    cond = torch.from_numpy(z["inf/cond"]).cuda()
-    m = _model(704, mode, nc)
-    out = m.infer(cond, seed=7).cpu().numpy()
-    assert out.shape == steps[-1].shape
-    T = SCHED[1]
-    record = torch.empty((T,) + tuple(cond.shape), dtype=torch.float32, device="cuda")
-    out2 = torch.empty_like(cond)
-    m._context(cond.device).sample_continuous(cond, out2, record, 1, 7, 0)
-    errs = [rms(record[i].cpu().numpy(), steps[i]) for i in range(T)]
-    print(f"CAUNet {nc} {mode}: rms of x_t per step {['%.2e' % e for e in errs]}")
-    for e, s in zip(errs, steps):
-        assert e <= 1e-4 * _gate(s)
-    assert torch.equal(out2.cpu(), torch.from_numpy(out))
+    S.check_sampling_matches_reference(CASE, nc, mode)
 
 
 def test_row_sharding_is_bit_identical(torch_cuda):
-    """Rows sampled in two shards (row_offset) equal the rows of one batch; sharded_infer without a
-    process group is model.infer."""
-    import model.model as M
-    m = _model(704, "conditional", dtype="bfloat16")
-    cond = torch.from_numpy(_inputs(4, 704, seed=1)[0]).cuda()
-    full = m.infer(cond, seed=11)
-    a = m.infer(cond[:2].contiguous(), seed=11, row_offset=0)
-    b = m.infer(cond[2:].contiguous(), seed=11, row_offset=2)
-    assert torch.isfinite(full).all() and float(full.abs().max()) > 0
-    assert torch.equal(full, torch.cat([a, b]))
-    assert torch.equal(M.sharded_infer(m, cond, seed=11), full)
+    S.check_row_sharding(CASE)
 
 
 def _paths():
@@ -299,11 +228,8 @@ def _rank(rank, world, port, out_path):
 def test_two_ranks_equal_single_run(torch_cuda, tmp_path):
     """sharded_infer in two spawned ranks that share cuda:0 and gather over gloo; an odd batch, so the
     last rank's shard is padded."""
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
+    from _helpers import free_port
+    port = free_port()
     sharded = str(tmp_path / "sharded.npy")
     mp.spawn(_rank, args=(2, port, sharded), nprocs=2, join=True)
     a = np.load(sharded)
@@ -314,85 +240,18 @@ def test_two_ranks_equal_single_run(torch_cuda, tmp_path):
 
 # ---- 14: SDDM.forward, configure-time refusals, infer.py
 def test_sddm_forward_matches_oracle(torch_cuda):
-    """SDDM.forward (evaluation only): q-sample at fixed t, then the network."""
-    B, N = 2, 704
-    rng = np.random.default_rng(23)
-    target = torch.from_numpy(rng.uniform(-0.5, 0.5, (B, 1, N)).astype(np.float32)).cuda()
-    cond = (target + torch.from_numpy(rng.uniform(-0.1, 0.1, (B, 1, N)).astype(np.float32)).cuda())
-    noise = torch.from_numpy(rng.standard_normal((B, 1, N)).astype(np.float32)).cuda()
-    m = _model(N)
-    with torch.no_grad():
-        predicted, got_noise = m(target, cond, noise=noise, t=torch.tensor([3, 1]), random_step=torch.tensor([0.25, 0.75]))
-    assert torch.equal(got_noise, noise) and tuple(predicted.shape) == (B, 1, N)
-    x_t, level, _ = m.diffusion.q_stochastic(target, noise, t=torch.tensor([3, 1]), random_step=torch.tensor([0.25, 0.75]))
-    ref = O.forward(_params(), cond.cpu().numpy(), x_t.cpu().numpy(), level.cpu().numpy())
-    err = rms(predicted.cpu().numpy(), ref)
-    print(f"CAUNet SDDM.forward: rms vs oracle {err:.3e}")
-    assert err <= 1e-4 * _gate(ref)
-
-
-def _cfg(**change):
-    return {"arch": {"type": "SDDM", "args": {}},
-            "diffusion": {"type": "GaussianDiffusion", "args": {"schedule": "linear", "n_timestep": 3}},
-            "network": {"type": "CAUNet", "args": _args(**change)}, "num_samples": 704}
+    S.check_sddm_forward_matches_oracle(CASE)
 
 
 @pytest.mark.parametrize("name,value", [("inner_channel", 32), ("n_encode_layers", 3), ("dense_depth", 5), ("segment_len", 256),
                                         ("segment_stride", 32), ("n_TSTB", 0)])
 def test_unsupported_arguments_are_refused_at_configure(torch_cuda, name, value):
-    import sddm_hip
-    with pytest.raises(NotImplementedError, match=name):
-        sddm_hip.Context(_cfg(**{name: value}), 0)
+    S.check_refused_at_configure(CASE, S.config(CASE, 704, **{name: value}), name)
 
 
 def test_context_registers_the_reference_keys(torch_cuda):
-    import sddm_hip
-    ctx = sddm_hip.Context(_cfg(), 0)
-    assert ctx.missing() == 450
-    ctx.close()
-
-
-def _write_pcm16(path, x, sr=16000):
-    pcm = np.clip(np.round(x * 32768), -32768, 32767).astype("<i2").tobytes()
-    hdr = struct.pack("<4sI4s4sIHHIIHH4sI", b"RIFF", 36 + len(pcm), b"WAVE", b"fmt ", 16, 1, 1, sr, 2 * sr, 2, 16,
-                      b"data", len(pcm))
-    with open(path, "wb") as f:
-        f.write(hdr + pcm)
+    S.check_missing_params(CASE)
 
 
 def test_infer_cli_end_to_end(torch_cuda, tmp_path):
-    """infer.py with configs/config_caunet.json at chunks of 704 samples and T = 3: WAV in, chunk,
-    denoise, stitch, WAV out."""
-    import infer
-    import model.diffusion as D
-    import model.model as M
-    from data_loader import wav_io
-    from parse_config import ConfigParser, read_json
-    N = 704
-    rng = np.random.default_rng(4)
-    for d in ("clean", "noisy"):
-        os.makedirs(tmp_path / "data" / d)
-    lengths = [1800, 500]
-    for i, n in enumerate(lengths):
-        c = 0.3 * np.sin(np.arange(n) * 0.05)
-        _write_pcm16(tmp_path / "data" / "clean" / f"u{i}.wav", c)
-        _write_pcm16(tmp_path / "data" / "noisy" / f"u{i}.wav", c + rng.uniform(-0.05, 0.05, n))
-    cfg = read_json(os.path.join(os.path.dirname(infer.__file__), "configs", "config_caunet.json"))
-    assert cfg["network"]["type"] == "CAUNet" and cfg["num_samples"] == 16448
-    cfg["num_samples"] = N
-    cfg["diffusion"]["args"].update({"n_timestep": 3, "linear_end": 0.05})
-    cfg["infer_dataset"]["args"]["data_root"] = str(tmp_path / "data")
-    cfg["infer_data_loader"]["args"].update({"batch_size": 1, "num_workers": 0})
-    cfg["trainer"]["save_dir"] = str(tmp_path / "runs")
-    ref_model = M.SDDM(D.GaussianDiffusion("linear", 3, 1e-4, 0.05, device="cpu"), _net(N))
-    ck = tmp_path / "model_best.pth"
-    torch.save({"arch": "SDDM", "epoch": 1,
-                "state_dict": {"module." + k: v.cpu() for k, v in ref_model.state_dict().items()},
-                "config": json.loads(json.dumps(cfg))}, ck)
-    config = ConfigParser(cfg, resume=ck, run_id="e2e")
-    log = infer.main(config, seed=100)
-    assert np.isfinite(log["loss"])
-    for i, n in enumerate(lengths):
-        out, sr = wav_io.load(os.path.join(str(config.save_dir), "samples", "output", f"u{i}.wav"))
-        assert sr == 16000 and out.shape[1] % N == 0 and out.shape[1] >= n
-        assert torch.isfinite(out).all() and float(out.abs().max()) > 0
+    S.check_infer_cli_end_to_end(CASE, tmp_path)

@@ -2,23 +2,14 @@
 the HIP device -> stitched WAVs -- and each written file equals SDDM.infer of its chunks."""
 import json
 import os
-import struct
 
 import numpy as np
 import pytest
 import torch
 
-from _helpers import unet_config, unet_params
+from _helpers import unet_config, unet_params, write_pcm16
 
 pytestmark = pytest.mark.gpu
-
-
-def _write_pcm16(path, x, sr=16000):
-    pcm = np.clip(np.round(x * 32768), -32768, 32767).astype("<i2").tobytes()
-    hdr = struct.pack("<4sI4s4sIHHIIHH4sI", b"RIFF", 36 + len(pcm), b"WAVE", b"fmt ", 16, 1, 1, sr, 2 * sr, 2, 16,
-                      b"data", len(pcm))
-    with open(path, "wb") as f:
-        f.write(hdr + pcm)
 
 
 def test_infer_cli_end_to_end(torch_cuda, tmp_path):
@@ -35,8 +26,8 @@ def test_infer_cli_end_to_end(torch_cuda, tmp_path):
     lengths = [5000, 1000]
     for i, n in enumerate(lengths):
         c = 0.3 * np.sin(np.arange(n) * 0.05)
-        _write_pcm16(tmp_path / "data" / "clean" / f"u{i}.wav", c)
-        _write_pcm16(tmp_path / "data" / "noisy" / f"u{i}.wav", c + rng.uniform(-0.05, 0.05, n))
+        write_pcm16(tmp_path / "data" / "clean" / f"u{i}.wav", c)
+        write_pcm16(tmp_path / "data" / "noisy" / f"u{i}.wav", c + rng.uniform(-0.05, 0.05, n))
     cfg = unet_config(N, sched=("linear", 3, 1e-4, 0.05))
     cfg.update({"name": "cli", "sample_rate": 16000, "loss": "l1_loss",
                 "infer_dataset": {"type": "InferDataset", "args": {"data_root": str(tmp_path / "data"),

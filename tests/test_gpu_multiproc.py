@@ -60,11 +60,8 @@ def _single(rank, out_path):
 
 
 def test_two_ranks_on_the_library_equal_single_run(tmp_path):
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
+    from _helpers import free_port
+    port = free_port()
     sharded, single = str(tmp_path / "sharded.npy"), str(tmp_path / "single.npy")
     mp.spawn(_rank, args=(2, port, sharded), nprocs=2, join=True)
     mp.spawn(_single, args=(single,), nprocs=1, join=True)
@@ -98,11 +95,8 @@ def test_rccl_collectives_of_the_sharded_path(tmp_path):
     group, sharded_infer's seed broadcast of a device tensor and _all_gather_rows'
     all_gather_into_tensor of the sampled rows; the gathered rows equal a single-process run bit
     for bit.  (RCCL refuses two ranks on one device; the 1/2/4/8-GPU curve is the driver's run.)"""
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
+    from _helpers import free_port
+    port = free_port()
     rccl, single = str(tmp_path / "rccl.npy"), str(tmp_path / "single.npy")
     mp.spawn(_rccl_rank, args=(port, rccl), nprocs=1, join=True)
     mp.spawn(_single, args=(single,), nprocs=1, join=True)

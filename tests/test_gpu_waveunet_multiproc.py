@@ -55,11 +55,8 @@ def _rank(rank, world, port, out_path):
 
 
 def test_two_ranks_equal_single_run(torch_cuda, tmp_path):
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
+    from _helpers import free_port
+    port = free_port()
     sharded = str(tmp_path / "sharded.npy")
     mp.spawn(_rank, args=(2, port, sharded), nprocs=2, join=True)
     a = np.load(sharded)

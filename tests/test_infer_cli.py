@@ -3,19 +3,12 @@ InferDataset chunking / collate / regrouping (data_loaders.py:101-164, infer.py:
 checkpoint reader (base_trainer.py:108-128) and SI-SNR (model/metric.py:5-34)."""
 import os
 import pathlib
-import struct
 
 import numpy as np
 import pytest
 import torch
 
-
-def _write_pcm16(path, x, sr=16000):
-    pcm = np.clip(np.round(x * 32768), -32768, 32767).astype("<i2").tobytes()
-    hdr = struct.pack("<4sI4s4sIHHIIHH4sI", b"RIFF", 36 + len(pcm), b"WAVE", b"fmt ", 16, 1, 1, sr, 2 * sr, 2, 16,
-                      b"data", len(pcm))
-    with open(path, "wb") as f:
-        f.write(hdr + pcm)
+from _helpers import write_pcm16
 
 
 def test_wav_float_roundtrip_and_pcm16_scaling(tmp_path):
@@ -24,7 +17,7 @@ def test_wav_float_roundtrip_and_pcm16_scaling(tmp_path):
     wav_io.save(tmp_path / "a.wav", x, 16000)
     y, sr = wav_io.load(tmp_path / "a.wav")
     assert sr == 16000 and torch.equal(x, y)
-    _write_pcm16(tmp_path / "b.wav", np.array([0.5, -1.0, 0.25]))
+    write_pcm16(tmp_path / "b.wav", np.array([0.5, -1.0, 0.25]))
     y, _ = wav_io.load(tmp_path / "b.wav")
     assert y.tolist() == [[0.5, -1.0, 0.25]]
 
@@ -36,8 +29,8 @@ def _dataset(tmp_path, lengths, T):
         os.makedirs(tmp_path / d, exist_ok=True)
     for i, n in enumerate(lengths):
         c = rng.uniform(-0.5, 0.5, n)
-        _write_pcm16(tmp_path / "clean" / f"f{i}.wav", c)
-        _write_pcm16(tmp_path / "noisy" / f"f{i}.wav", c + rng.uniform(-0.1, 0.1, n))
+        write_pcm16(tmp_path / "clean" / f"f{i}.wav", c)
+        write_pcm16(tmp_path / "noisy" / f"f{i}.wav", c + rng.uniform(-0.1, 0.1, n))
     return D.InferDataset(str(tmp_path), ".wav", sample_rate=16000, T=T)
 
 

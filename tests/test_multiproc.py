@@ -42,11 +42,8 @@ def _worker(rank, world, port, out_path):
 
 
 def test_two_rank_gather_equals_single_run(tmp_path):
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
+    from _helpers import free_port
+    port = free_port()
     out_path = str(tmp_path / "gathered.npy")
     mp.spawn(_worker, args=(2, port, out_path), nprocs=2, join=True)
     from oracle import sampler, unet
@@ -83,11 +80,8 @@ def _spec_worker(rank, world, port, out_path):
 
 def test_two_rank_spectrogram_gather_equals_single_run(tmp_path):
     """The same sharding contract for SDDM_spectrogram (WaveGrad): rows keyed by global index."""
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
+    from _helpers import free_port
+    port = free_port()
     out_path = str(tmp_path / "gathered_wg.npy")
     mp.spawn(_spec_worker, args=(2, port, out_path), nprocs=2, join=True)
     from oracle import sampler, wavegrad as wg
@@ -137,11 +131,8 @@ def test_sharded_infer_helper_two_ranks(tmp_path):
     """model.model.sharded_infer (the product multi-GPU entry point used by infer.py and bench.py):
     padding of B=3 to a multiple of 2, contiguous row blocks with row_offset, one all-gather; the
     result equals the single-process run of all rows bit for bit."""
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
+    from _helpers import free_port
+    port = free_port()
     out_path = str(tmp_path / "sharded.npy")
     mp.spawn(_facade_worker, args=(2, port, out_path), nprocs=2, join=True)
     from sddm_hip.synth import noisy_speech
@@ -154,11 +145,8 @@ def test_sharded_infer_helper_two_ranks(tmp_path):
 def test_sharded_infer_helper_four_ranks_padded(tmp_path):
     """world size 4 with B=5: two rows per rank, 3 padded rows on the last ranks (rank 3 samples
     only padding), one all-gather; the gathered [:5] equals a single run of the 5 rows bit for bit."""
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
+    from _helpers import free_port
+    port = free_port()
     out_path = str(tmp_path / "sharded4.npy")
     mp.spawn(_facade_worker, args=(4, port, out_path, 5), nprocs=4, join=True)
     from sddm_hip.synth import noisy_speech
