@@ -60,8 +60,8 @@ void sddm_destroy(sddm_ctx* ctx);
  * parse_config.py:82-95).  `json` is {"arch": {...}, "diffusion": {...}, "network": {...},
  * "num_samples": N} with the reference's type names and args verbatim
  * (config_unet.json, config_diffwave.json, config_wavegrad.json, and the default config.json).
- * Network types: UNetModified2, UNetTST, CAUNet, DenoiseWaveGrad1, DenoiseWaveGrad3, Waveunet, Waveunet2
- * and Waveunet3 under arch SDDM
+ * Network types: UNetModified2, UNetTST, CAUNet, TSTNN, DenoiseWaveGrad1, DenoiseWaveGrad3, Waveunet,
+ * Waveunet2 and Waveunet3 under arch SDDM
  * (with its p_transition / noise_condition args); DiffWave and WaveGrad under arch
  * SDDM_spectrogram.  Any other pairing or type (DenoiseWaveGrad2 among them) returns
  * SDDM_ERR_NOT_IMPLEMENTED.  Waveunet3 is built for the network args of config_waveunet3.json
@@ -79,7 +79,10 @@ void sddm_destroy(sddm_ctx* ctx);
  * 32832 at the config's framing), and refuses anything else here.  CAUNet (config_caunet.json) is
  * built for inner_channel 64, n_encode_layers 4, dense_depth 3, segment_len 128, segment_stride 64,
  * n_TSTB >= 1 and use_affine_level false or true, and refuses any other value of them, naming the
- * argument; it needs no num_samples.  The 1-D networks need no num_samples: they take any positive
+ * argument; it needs no num_samples.  TSTNN (config_tstnn.json) is built for F 512, stride 256 and
+ * n_channels 64 and refuses any other value of them, naming the argument; it needs no num_samples and
+ * never reads the noise level.  A context around a stand-alone block may add num_layers >= 1 (the
+ * network's own Dual_Transformer has 4).  The 1-D networks need no num_samples: they take any positive
  * multiple of their hop (see sddm_sample). */
 int sddm_configure(sddm_ctx* ctx, const char* json);
 
@@ -101,7 +104,7 @@ int sddm_missing_params(sddm_ctx* ctx, int64_t* n_missing);
  * Geometry: UNetModified2 N = num_samples; DiffWave N = 256 frames; WaveGrad N = 300 frames;
  * DenoiseWaveGrad1 N a positive multiple of 400 (2*2*4*5*5); DenoiseWaveGrad3 of 300 (2*2*3*5*5);
  * Waveunet2 and Waveunet3 of 8 (three stride-2 levels); Waveunet of 2048 (eleven); CAUNet
- * N = 128 + 64 k (whole frames).
+ * N = 128 + 64 k and TSTNN N = 512 + 256 k (whole frames).
  * Anything else returns SDDM_ERR_SHAPE before any launch. */
 int sddm_sample(sddm_ctx* ctx, const float* cond, int64_t B, int64_t N, uint64_t seed,
                 int64_t row_offset, float* out, void* stream);
@@ -123,7 +126,7 @@ int sddm_sample_continuous(sddm_ctx* ctx, const float* cond, int64_t B, int64_t 
 
 /* Replaces one noise_estimate_model(condition, x_t, noise_level) call (model.py:110):
  * noise_level: [B] fp32 device.  eps_out: [B, 1, N] fp32 device.  cond is [B, 1, N] for
- * UNetModified2, UNetTST, CAUNet, DenoiseWaveGrad1, DenoiseWaveGrad3, Waveunet, Waveunet2 and Waveunet3 (the noisy waveform; N
+ * UNetModified2, UNetTST, CAUNet, TSTNN, DenoiseWaveGrad1, DenoiseWaveGrad3, Waveunet, Waveunet2 and Waveunet3 (the noisy waveform; N
  * as in sddm_sample) and the spectrogram [B, bins, frames] for DiffWave and WaveGrad.  The output of
  * Waveunet, Waveunet2 and Waveunet3 is clamped to [-1, 1] (waveunet.py:503-504, waveunet2.py:321-322, waveunet3.py:414-415, eval
  * mode). */
@@ -137,7 +140,10 @@ int sddm_network_forward(sddm_ctx* ctx, const float* cond, const float* x_t,
  * in the context's compute dtype, so in a 16-bit context the input and the output are rounded to it.
  * dim2 * dim1 above 64 returns SDDM_ERR_NOT_IMPLEMENTED.  On a context configured for network CAUNet it
  * is Dual_Transformer(64, 64, 0, n_TSTB) (model/CAUNet.py:180-201): in, out [B, 64, dim2, dim1], any
- * dim2 and dim1 with B * dim2 * dim1 up to 2^24.  Returns after the result is complete. */
+ * dim2 and dim1 with B * dim2 * dim1 up to 2^24.  On a context configured for network TSTNN it is that
+ * network's Dual_Transformer(64, 64, num_layers=4) (model/tstnn.py:143-164: single-slope PReLUs, the
+ * output PReLU before its conv), with the same shapes and limits as CAUNet's; the parameters that need
+ * to be loaded are the context's dual_transformer.*.  Returns after the result is complete. */
 int sddm_dual_transformer(sddm_ctx* ctx, const float* in, int64_t B, int64_t dim2, int64_t dim1,
                           float* out, void* stream);
 

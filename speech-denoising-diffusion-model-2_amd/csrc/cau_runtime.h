@@ -77,7 +77,7 @@ static std::map<std::string, std::vector<int64_t>> cau_param_shapes(const CAUSta
       s[p + "upsample.2.weight"] = {64};
     }
   }
-  dt_param_shapes(s, "mid", kCauC, d.n_tstb, true);       // CAUNet.py:152-178: one PReLU slope per channel
+  dt_param_shapes(s, "mid", kCauC, d.n_tstb, kDtPreluPerChannel);       // CAUNet.py:152-178: one PReLU slope per channel
   s["final_conv.weight"] = {1, 64, 1, 1}; s["final_conv.bias"] = {1};
   return s;
 }
@@ -123,7 +123,7 @@ size_t CAUState::pack(sddm_ctx* c, WeightPacker& pk) {
     cat(w2, P(p + "noise_func.noise_func.2.weight")); cat(b2, P(p + "noise_func.noise_func.2.bias"));
   }
   pk.f32("mlp.w1", w1); pk.f32("mlp.b1", b1); pk.f32("mlp.a1", a1); pk.f32("mlp.w2", w2); pk.f32("mlp.b2", b2);
-  dt_pack(c, pk, "mid", kCauLayout, n_tstb);           // at the offsets of caunet.h
+  dt_pack(c, pk, "mid", kCauLayout, n_tstb, kDtPreluPerChannel);           // at the offsets of caunet.h
   pk.f32("final.w", P("final_conv.weight"));
   pk.f32("final.b", P("final_conv.bias"));
   return 0;                                            // no table of its own: the level is one scalar per t

@@ -94,6 +94,8 @@ struct CauDtArgs {
   const void* wmat; const float* wvec;
   char* ws;                   // cau_dt_ws_bytes(dtype, B, dim2 * dim1) bytes
   int B, dim2, dim1, n_tstb;
+  int prelu_first;            // the output stage of tstnn.py:139-141: PReLU (the 32 slopes at kCauVOutA), then
+                              // the conv with its bias and nothing after it; 0: conv, then PReLU(64) (CAUNet)
 };
 size_t cau_dt_ws_bytes(int dtype, int64_t B, int64_t P);
 // 2 + 10 n_tstb launches: input conv; per encoder in_proj, attention, out_proj + norm1, GRU,

@@ -19,50 +19,16 @@
 // x += GroupNorm(src) as it loads.
 #include "caunet.h"
 
-#include "conv_common.h"
+#include "cau_frag.h"
 
 namespace sddm {
 namespace {
 
-template <typename T> __device__ __forceinline__ Frag<T> zero_frag() {
-  if constexpr (sizeof(T) == 4) {
-    return {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-  } else {
-    Frag<T> f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f.v[j] = (T)0.f;
-    return f;
-  }
-}
-// eight fp32 values -> a fragment (rounded to T: where an activation enters an MFMA)
-template <typename T> __device__ __forceinline__ Frag<T> frag_from_f32(f32x4 lo, f32x4 hi) {
-  if constexpr (sizeof(T) == 4) {
-    return {lo, hi};
-  } else {
-    Frag<T> f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { f.v[j] = (T)lo[j]; f.v[4 + j] = (T)hi[j]; }
-    return f;
-  }
-}
-template <typename T> __device__ __forceinline__ void frag_to_f32(const Frag<T>& f, f32x4& lo, f32x4& hi) {
-  if constexpr (sizeof(T) == 4) {
-    lo = f.lo; hi = f.hi;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { lo[j] = (float)f.v[j]; hi[j] = (float)f.v[4 + j]; }
-  }
-}
-template <typename T> __device__ __forceinline__ Frag<T> load_t(const T* p) { return load_frag<T>((const char*)p); }
-template <typename T> __device__ __forceinline__ Frag<T> load_wgt(const T* w, int nt, int KC, int kc, int lane) {
-  return load_frag<T>((const char*)(w + ((size_t)(nt * KC + kc) * 64 + lane) * 8));
-}
 __device__ __forceinline__ float cau_level(const WULevel& lv, int b) {
   if (lv.levels) return lv.levels[b];
   const int t = *lv.t_dev;
   return lv.time_step ? (float)t : lv.table[t];
 }
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ---------------------------------------------------------------------------------------------
 // first_conv, the noise MLPs, final_conv + overlap-add
@@ -297,7 +263,8 @@ template <typename T, int MODE> __global__ __launch_bounds__(256) void cau_conv_
 // ---------------------------------------------------------------------------------------------
 // Dual_Transformer: per-token kernels.  A block is four waves of 16 tokens of one image.
 // ---------------------------------------------------------------------------------------------
-enum { TOK_IN = 0, TOK_QKV = 1, TOK_PROJ = 2, TOK_LIN2 = 3, TOK_OUT = 4 };
+// TOK_OUTP: the output stage of tstnn.py:139-141, PReLU before the conv and nothing after it
+enum { TOK_IN = 0, TOK_QKV = 1, TOK_PROJ = 2, TOK_LIN2 = 3, TOK_OUT = 4, TOK_OUTP = 5 };
 struct CauTokArgs {
   int B, P;                     // images, tokens per image
   const void* xin;              // IN: x [tok][64]; PROJ: attention [tok][32]; LIN2: ReLU(GRU) [tok][128] (T)
@@ -338,7 +305,7 @@ template <typename T, int MODE> __global__ __launch_bounds__(256) void cau_tok_k
       for (int i = 0; i < 4; ++i) v[i] = v[i] >= 0.f ? v[i] : al[i] * v[i];
       if (valid) *(f32x4*)(a.cur + gt * 32 + c) = v;
     }
-  } else if constexpr (MODE == TOK_QKV || MODE == TOK_OUT) {
+  } else if constexpr (MODE == TOK_QKV || MODE == TOK_OUT || MODE == TOK_OUTP) {
     // cur += GroupNorm(1, 32, eps 1e-8)(gsrc) over the image: Chan's combination of the tile partials
     f32x4 lo = *(const f32x4*)(a.cur + gt * 32 + 8 * g), hi = *(const f32x4*)(a.cur + gt * 32 + 8 * g + 4);
     if (a.gsrc) {
@@ -362,6 +329,14 @@ template <typename T, int MODE> __global__ __launch_bounds__(256) void cau_tok_k
         *(f32x4*)(a.cur + gt * 32 + 8 * g + 4) = hi;
       }
     }
+    if constexpr (MODE == TOK_OUTP) {
+      const f32x4 alo = *(const f32x4*)(a.alpha + 8 * g), ahi = *(const f32x4*)(a.alpha + 8 * g + 4);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        lo[i] = lo[i] >= 0.f ? lo[i] : alo[i] * lo[i];
+        hi[i] = hi[i] >= 0.f ? hi[i] : ahi[i] * hi[i];
+      }
+    }
     const Frag<T> bx = frag_from_f32<T>(lo, hi);
     constexpr int NT = MODE == TOK_QKV ? 6 : 4;
 #pragma unroll
@@ -373,10 +348,12 @@ template <typename T, int MODE> __global__ __launch_bounds__(256) void cau_tok_k
       if constexpr (MODE == TOK_QKV) {
         if (nt < 2) v *= 0.35355339059327373f;                   // q scaled by head_dim^-0.5 = 8^-0.5
         if (valid) store4<T>((T*)a.out + gt * 96 + c, v[0], v[1], v[2], v[3]);
-      } else {
+      } else if constexpr (MODE == TOK_OUT) {
         const f32x4 al = *(const f32x4*)(a.alpha + c);
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = v[i] >= 0.f ? v[i] : al[i] * v[i];
+        if (valid) store4<T>((T*)a.out + gt * 64 + c, v[0], v[1], v[2], v[3]);
+      } else {
         if (valid) store4<T>((T*)a.out + gt * 64 + c, v[0], v[1], v[2], v[3]);
       }
     }
@@ -647,7 +624,8 @@ template <typename T> hipError_t cau_dt_run(const CauDtArgs& a, hipStream_t s) {
     CauTokArgs x = t;
     x.gsrc = s2; x.part = part; x.gnw = gnw; x.gnb = gnb;
     x.w = wm + kCauWOut; x.bias = wv + kCauVOutB; x.alpha = wv + kCauVOutA; x.out = a.out;
-    hipLaunchKernelGGL((cau_tok_kernel<T, TOK_OUT>), tgrid, blk, 0, s, x);
+    if (a.prelu_first) hipLaunchKernelGGL((cau_tok_kernel<T, TOK_OUTP>), tgrid, blk, 0, s, x);
+    else hipLaunchKernelGGL((cau_tok_kernel<T, TOK_OUT>), tgrid, blk, 0, s, x);
   }
   return hipGetLastError();
 }

@@ -7,7 +7,8 @@
 //   WaveGrad, DenoiseWaveGrad1 / 3  wg_runtime.h   >  sequential networks: each implements SeqNet, and
 //   Waveunet3            wu_runtime.h  |   seq_sample / seq_forward here drive whichever is configured
 //   Waveunet2, Waveunet  wu2_runtime.h |
-//   CAUNet               cau_runtime.h /
+//   CAUNet               cau_runtime.h |
+//   TSTNN                tstnn_runtime.h /
 // A further sequential network is one such header and one branch on net_type in sddm_configure.
 //
 // Reference counterparts:
@@ -35,6 +36,7 @@
 #include "kernels.h"
 #include "dual_transformer.h"
 #include "caunet.h"
+#include "tstnn.h"
 #include "q_kernels.h"
 #include "stft_kernels.h"
 #include "sddm_common.h"
@@ -157,8 +159,8 @@ struct Net {
 
 // A sequential network: its forward is one launch sequence on the caller's stream.  DiffWave
 // (dw_runtime.h), the WaveGrad family (wg_runtime.h), Waveunet3 (wu_runtime.h), Waveunet2 and Waveunet
-// (wu2_runtime.h) and CAUNet (cau_runtime.h) derive from it; seq_sample / seq_forward below drive any
-// of them.  UNetModified2 (unet_runtime.h) runs in lanes and graphs instead
+// (wu2_runtime.h), CAUNet (cau_runtime.h) and TSTNN (tstnn_runtime.h) derive from it; seq_sample /
+// seq_forward below drive any of them.  UNetModified2 (unet_runtime.h) runs in lanes and graphs instead
 struct SeqNet : Net {
   std::map<std::string, size_t> woff;                  // packed weights in ctx->warena
   size_t off_sp = 0, off_rows = 0;                      // StepParams; the path's rows of every t (`pack`)
@@ -290,14 +292,22 @@ static void store_frags(void* dst, size_t off, const float* w, int N, int K, int
 
 // ---------------------------------------------------------------------------------------------
 // Dual_Transformer(C, C, 0, n_tstb), the mid block of UNetTST (UNetTST.py:184-210) and of CAUNet
-// (CAUNet.py:152-178): state-dict shapes and weight packing, d_model = C / 2, GRU hidden C
+// (CAUNet.py:152-178) and TSTNN's dual_transformer (tstnn.py:114-141): state-dict shapes and weight
+// packing, d_model = C / 2, GRU hidden C
 // ---------------------------------------------------------------------------------------------
-// prelu_per_channel: input.1 / output.1 hold one slope per channel (CAUNet), else one in all (UNetTST)
+// The block's two PReLUs.  Shared: input.1 / output.1 hold one slope in all (UNetTST).  PerChannel:
+// one slope per channel (CAUNet).  SharedFirst: one slope each and output = (PReLU, Conv2d), so the
+// keys are output.0.weight [1], output.1.weight, output.1.bias (TSTNN); dt_pack broadcasts the two
+// slopes into the layout's per-channel slots
+enum DtPrelu { kDtPreluShared = 0, kDtPreluPerChannel = 1, kDtPreluSharedFirst = 2 };
 static void dt_param_shapes(std::map<std::string, std::vector<int64_t>>& s, const std::string& n, int64_t C, int n_tstb,
-                            bool prelu_per_channel) {
+                            DtPrelu prelu) {
   const int64_t d = C / 2;
-  s[n + ".input.0.weight"] = {d, C, 1, 1}; s[n + ".input.0.bias"] = {d}; s[n + ".input.1.weight"] = {prelu_per_channel ? d : 1};
-  s[n + ".output.0.weight"] = {C, d, 1, 1}; s[n + ".output.0.bias"] = {C}; s[n + ".output.1.weight"] = {prelu_per_channel ? C : 1};
+  const bool per_channel = prelu == kDtPreluPerChannel;
+  const char* oc = prelu == kDtPreluSharedFirst ? ".output.1" : ".output.0";   // the output conv, and its PReLU
+  const char* op = prelu == kDtPreluSharedFirst ? ".output.0" : ".output.1";
+  s[n + ".input.0.weight"] = {d, C, 1, 1}; s[n + ".input.0.bias"] = {d}; s[n + ".input.1.weight"] = {per_channel ? d : 1};
+  s[n + oc + ".weight"] = {C, d, 1, 1}; s[n + oc + ".bias"] = {C}; s[n + op + ".weight"] = {per_channel ? C : 1};
   for (int i = 0; i < n_tstb; ++i)
     for (const char* pass : {"row", "col"}) {
       const std::string e = n + "." + pass + "_trans." + std::to_string(i);
@@ -337,7 +347,7 @@ static const DtLayout kCauLayout = {   // caunet.h
     kCauEncV};
 
 // packs the block `n` ("mid") as the blobs n.wmat and n.wvec
-static void dt_pack(sddm_ctx* c, WeightPacker& pk, const std::string& n, const DtLayout& L, int n_tstb) {
+static void dt_pack(sddm_ctx* c, WeightPacker& pk, const std::string& n, const DtLayout& L, int n_tstb, DtPrelu prelu) {
   const int dt = c->dtype, ne = 2 * n_tstb;
   auto P = [&](const std::string& k) -> const std::vector<float>& { return c->params.at(k).data; };
   char* wm = pk.raw(n + ".wmat", ((size_t)L.WEnc0 + (size_t)ne * L.EncW) * dtype_size(dt));
@@ -345,11 +355,18 @@ static void dt_pack(sddm_ctx* c, WeightPacker& pk, const std::string& n, const D
   auto frag = [&](size_t off, const std::vector<float>& w, int N, int K) { store_frags(wm, off, w.data(), N, K, dt); };
   auto vec = [&](size_t off, const std::vector<float>& v) { std::copy(v.begin(), v.end(), wv.begin() + off); };
   frag(L.WIn, P(n + ".input.0.weight"), L.D, L.C);
-  frag(L.WOut, P(n + ".output.0.weight"), L.C, L.D);
   vec(L.VInB, P(n + ".input.0.bias"));
-  vec(L.VInA, P(n + ".input.1.weight"));
-  vec(L.VOutB, P(n + ".output.0.bias"));
-  vec(L.VOutA, P(n + ".output.1.weight"));
+  if (prelu == kDtPreluSharedFirst) {
+    frag(L.WOut, P(n + ".output.1.weight"), L.C, L.D);
+    vec(L.VOutB, P(n + ".output.1.bias"));
+    vec(L.VInA, std::vector<float>(L.D, P(n + ".input.1.weight")[0]));
+    vec(L.VOutA, std::vector<float>(L.C, P(n + ".output.0.weight")[0]));   // the conv's D inputs read the first D
+  } else {
+    frag(L.WOut, P(n + ".output.0.weight"), L.C, L.D);
+    vec(L.VOutB, P(n + ".output.0.bias"));
+    vec(L.VInA, P(n + ".input.1.weight"));
+    vec(L.VOutA, P(n + ".output.1.weight"));
+  }
   for (int e = 0; e < ne; ++e) {
     const char* pass = e % 2 ? "col" : "row";
     const std::string p = n + "." + pass + "_trans." + std::to_string(e / 2);
@@ -479,6 +496,7 @@ int SeqNet::forward(sddm_ctx* c, const float* cond, const float* x_t, const floa
 #include "wu_runtime.h"
 #include "wu2_runtime.h"
 #include "cau_runtime.h"
+#include "tstnn_runtime.h"
 #include "unet_runtime.h"
 
 // =============================================================================================
@@ -671,6 +689,13 @@ int sddm_configure(sddm_ctx* c, const char* json) {
     const auto shapes = cau_param_shapes(*us);
     return finish_configure(c, T, tabs, shapes, std::move(us), -1);
   }
+  if (c->net_type == "TSTNN") {                                  // tstnn.py:216-299, config_tstnn.json
+    TRY(needs_arch(c, "TSTNN", "SDDM"));
+    auto us = std::make_unique<TSTNNState>();
+    TRY(tstnn_check_config(net.at("args"), *us));
+    const auto shapes = tstnn_param_shapes(*us);
+    return finish_configure(c, T, tabs, shapes, std::move(us), -1);
+  }
   // UNetTST (UNetTST.py:270-392): UNetModified2 with mid = Dual_Transformer and no final Swish in the noise MLP
   const bool tst = c->net_type == "UNetTST";
   if (c->net_type != "UNetModified2" && !tst) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "network type '%s'", c->net_type.c_str());
@@ -771,13 +796,14 @@ int sddm_network_forward(sddm_ctx* c, const float* cond, const float* x_t, const
   return c->net->forward(c, cond, x_t, noise_level, B, N, eps_out, (hipStream_t)stream);
 }
 
-// The Dual_Transformer of a UNetTST or CAUNet context alone (UNetTST.py:212-233, CAUNet.py:180-201).
-// Only the mid.* parameters need to be loaded: parameters outside mid that are still missing are
-// packed as zeros
+// The Dual_Transformer of a UNetTST, CAUNet or TSTNN context alone (UNetTST.py:212-233,
+// CAUNet.py:180-201, tstnn.py:143-164).  Only the block's parameters (mid.*; TSTNN: dual_transformer.*)
+// need to be loaded: parameters outside it that are still missing are packed as zeros
 int sddm_dual_transformer(sddm_ctx* c, const float* in, int64_t B, int64_t dim2, int64_t dim1, float* out, void* stream) {
   if (!c || !c->configured) FAIL(SDDM_ERR_STATE, "context not configured");
-  const bool cau = c->net_type == "CAUNet";
-  if (c->net_type != "UNetTST" && !cau) FAIL(SDDM_ERR_STATE, "sddm_dual_transformer needs a context configured for UNetTST or CAUNet");
+  const bool tstnn = c->net_type == "TSTNN", cau = c->net_type == "CAUNet" || tstnn;   // cau: caunet.hip's kernels
+  if (c->net_type != "UNetTST" && !cau) FAIL(SDDM_ERR_STATE, "sddm_dual_transformer needs a context configured for UNetTST, CAUNet or TSTNN");
+  const std::string blk = tstnn ? "dual_transformer" : "mid";
   if (!in || !out) FAIL(SDDM_ERR_INVALID_ARG, "NULL tensor");
   if (B < 1 || B > 65535 || dim2 < 1 || dim1 < 1) FAIL(SDDM_ERR_INVALID_ARG, "shape B=%lld dim2=%lld dim1=%lld", (long long)B, (long long)dim2, (long long)dim1);
   if (!cau && dim2 * dim1 > kTstMaxTokens)
@@ -787,7 +813,7 @@ int sddm_dual_transformer(sddm_ctx* c, const float* in, int64_t B, int64_t dim2,
   SDDM_HIP_CHECK(hipSetDevice(c->device));
   for (auto& kv : c->params) {
     if (kv.second.loaded) continue;
-    if (kv.first.rfind("mid.", 0) == 0) FAIL(SDDM_ERR_STATE, "parameter %s not loaded", kv.first.c_str());
+    if (kv.first.rfind(blk + ".", 0) == 0) FAIL(SDDM_ERR_STATE, "parameter %s not loaded", kv.first.c_str());
     int64_t n = 1;
     for (int64_t d : kv.second.shape) n *= d;
     if ((int64_t)kv.second.data.size() != n) kv.second.data.assign((size_t)n, 0.f);
@@ -802,9 +828,10 @@ int sddm_dual_transformer(sddm_ctx* c, const float* in, int64_t B, int64_t dim2,
   SDDM_HIP_CHECK(hipMalloc(&buf, 2 * bytes + ws));
   hipError_t e = launch_dt_pack(c->dtype, in, buf, (int)B, C, P, s);
   if (cau) {
-    const CAUState& n = static_cast<const CAUState&>(*c->net);
-    CauDtArgs a{buf, buf + bytes, c->warena.base + n.woff.at("mid.wmat"), c->warena.at<float>(n.woff.at("mid.wvec")), buf + 2 * bytes,
-                (int)B, (int)dim2, (int)dim1, n.n_tstb};
+    const SeqNet& n = static_cast<const SeqNet&>(*c->net);
+    const int layers = tstnn ? static_cast<const TSTNNState&>(n).layers : static_cast<const CAUState&>(n).n_tstb;
+    CauDtArgs a{buf, buf + bytes, c->warena.base + n.woff.at(blk + ".wmat"), c->warena.at<float>(n.woff.at(blk + ".wvec")), buf + 2 * bytes,
+                (int)B, (int)dim2, (int)dim1, layers, tstnn ? 1 : 0};
     if (e == hipSuccess) e = launch_cau_dual_transformer(c->dtype, a, s);
   } else {
     const UNetState& n = static_cast<const UNetState&>(*c->net);

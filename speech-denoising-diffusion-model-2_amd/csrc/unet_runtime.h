@@ -160,7 +160,7 @@ static std::map<std::string, std::vector<int64_t>> unet_param_shapes(const UNetC
       s[n + ".weight"] = {L.cout, L.cin, 3, 3};
       s[n + ".bias"] = {L.cout};
     } else if (L.kind == 5) {   // Dual_Transformer (UNetTST.py:184-210): one-element PReLUs
-      dt_param_shapes(s, n, L.cin, c.n_tstb, false);
+      dt_param_shapes(s, n, L.cin, c.n_tstb, kDtPreluShared);
     } else {
       s[n + ".block.0.weight"] = {L.cin};
       s[n + ".block.0.bias"] = {L.cin};
@@ -312,7 +312,7 @@ int UNetState::upload_weights(sddm_ctx* c) {
       add_conv(n + ".w", P(n + ".conv.weight"), 9);
       pk.f32(n + ".b", P(n + ".conv.bias").data);
     } else if (L.kind == 5) {
-      dt_pack(c, pk, n, kTstLayout, u.n_tstb);   // at the offsets of dual_transformer.h
+      dt_pack(c, pk, n, kTstLayout, u.n_tstb, kDtPreluShared);   // at the offsets of dual_transformer.h
     } else {
       pk.f32(n + ".gamma", P(n + ".block.0.weight").data);
       pk.f32(n + ".beta", P(n + ".block.0.bias").data);

@@ -11,8 +11,13 @@ bidirectional GRU along the rows, then along the columns of the bottom level) in
 block is also a module of its own.  CAUNet (config_caunet.json) is a causal dense-block U-Net over the
 frames (dilated (2,3) convs with LayerNorm over the frame and PReLU, a strided downsample and a sub-pixel
 upsample) around the same block at d_model 32 (``model.CAUNet.Dual_Transformer``: per-channel PReLUs, any
-number of frames).  The reference's TSTNN and SNR-estimator networks are not built."""
+number of frames).  TSTNN (config_tstnn.json) frames at 512 / 256: a depth-4 dense block at the frame
+width, a strided conv to half of it, the block again (``model.tstnn.Dual_Transformer``: single-slope
+PReLUs, the output PReLU before its conv, four layers over 63 frames of 256 positions), a gated mask
+(tanh x sigmoid -> conv -> ReLU) on the encoder's output, a second dense block and a sub-pixel conv back;
+it ignores the noise level.  The reference's SNR-estimator networks are not built."""
 from .CAUNet import CAUNet  # noqa: F401
+from .tstnn import TSTNN  # noqa: F401
 from .UNetModified2 import UNetModified2  # noqa: F401
 from .UNetTST import Dual_Transformer, UNetTST  # noqa: F401
 from .diffwave import DiffWave  # noqa: F401

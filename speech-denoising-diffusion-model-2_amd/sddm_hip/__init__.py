@@ -183,7 +183,7 @@ class Context:
                                          _ptr(eps_out), _stream(torch, cond.device)))
 
     def dual_transformer(self, x, out):
-        """sddm_dual_transformer: x, out [B, 160, dim2, dim1] fp32 on the device (UNetTST contexts)."""
+        """sddm_dual_transformer: x, out [B, C, dim2, dim1] fp32 on the device (C = 160 in a UNetTST context, 64 in a CAUNet or TSTNN one)."""
         import torch
         B, _, dim2, dim1 = x.shape
         check(lib().sddm_dual_transformer(self._h, _ptr(x), B, dim2, dim1, _ptr(out), _stream(torch, x.device)))

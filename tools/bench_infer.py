@@ -4,7 +4,7 @@
                                 [--dtypes bfloat16,float16,float32] [--log profiles/NAME.log]
                                 [--no-kernels] [--no-unet]
 
-NAME is a key of NETWORKS: Waveunet, Waveunet2, Waveunet3, UNetTST, CAUNet or DenoiseWaveGrad; the
+NAME is a key of NETWORKS: Waveunet, Waveunet2, Waveunet3, UNetTST, CAUNet, TSTNN or DenoiseWaveGrad; the
 table gives the config file and the default batch and samples.  Cases: B x N samples in every dtype,
 `steps` reverse steps of the config's schedule (linear, 1e-6 .. 0.01).  Each case is one warm-up call
 (context, weight upload, workspace, code objects, plan and graph capture where the runtime has them),
@@ -20,13 +20,16 @@ launches_per_step restates the library's launch sequence, at any N:
              each, 6 ConvLayers of three launches, head, transition
   CAUNet     csrc/cau_runtime.h: first_conv 1, noise MLPs 1, 8 layers x 4 convs, the Dual_Transformer
              2 + 10 n_TSTB, final_conv 1, transition 1
+  TSTNN      csrc/tstnn_runtime.h: first 1, dense convs 4 + 4, down 1, up 1, the Dual_Transformer
+             2 + 10 * 4, gate 1, final 1, transition 1
   UNetTST    counted: a further profiled call (per-launch events, no graphs) gives the ops of one lane's
              step, and transformer_share, the Dual_Transformer op's part of the summed op times
 
-CAUNet: unless --no-kernels, one further call of 5 steps runs under torch.profiler and kernel_share
-gives every kernel family's part of the summed kernel time of that call (template arguments stripped),
-gru_us_per_recurrent_step the GRU kernels' time divided by the recurrent steps they ran (per reverse
-step 2 n_TSTB launches of dim1 or dim2 steps; the two directions run in one launch).
+CAUNet and TSTNN: unless --no-kernels, one further call of 5 steps runs under torch.profiler and
+kernel_share gives every kernel family's part of the summed kernel time of that call (template
+arguments stripped), gru_us_per_recurrent_step the GRU kernels' time divided by the recurrent steps they
+ran (per reverse step two launches per layer, of dim1 and of dim2 steps; the two directions run in one
+launch.  CAUNet: n_TSTB layers over [frames][8]; TSTNN: 4 layers over [frames][256]).
 
 UNetTST: unless --no-unet, every dtype is followed by the same case for UNetModified2 at the same
 arguments without n_TSTB: UNetTST is that network with mid.0's two convs swapped for the block, so the
@@ -51,6 +54,8 @@ SAMPLE_RATE = 16000
 PROFILE_STEPS = 5
 
 # config: the file under configs/ (None: no arguments, the reference config.json's schedule);
+# transformer: (layers, dim2, dim1) of the Dual_Transformer from the network's arguments and N, for the
+# networks whose profiled call reports kernel shares;
 # num_samples: the constructor takes the length; launches: launches_per_step, a number, a function of
 # the network's arguments, "ops" (counted from the profiled ops) or None (not reported);
 # cases: the (network, N) pairs of one dtype where they are not (NAME, --samples)
@@ -63,7 +68,11 @@ NETWORKS = {
                   "launches": 1 + 1 + 27 + 27 + 6 * 3 + 1 + 1},
     "UNetTST": {"config": "config_unettst.json", "batch": 16, "samples": 16448, "num_samples": True, "launches": "ops"},
     "CAUNet": {"config": "config_caunet.json", "batch": 16, "samples": 16448, "num_samples": True,
-               "launches": lambda a: 1 + 1 + 8 * 4 + 2 + 10 * a["n_TSTB"] + 1 + 1},
+               "launches": lambda a: 1 + 1 + 8 * 4 + 2 + 10 * a["n_TSTB"] + 1 + 1,
+               "transformer": lambda a, N: (a["n_TSTB"], (N - 128) // 64 + 1, 8)},
+    "TSTNN": {"config": "config_tstnn.json", "batch": 16, "samples": 16384, "num_samples": True,
+              "launches": 1 + (4 + 4) + 1 + 1 + (2 + 10 * 4) + 1 + 1 + 1,
+              "transformer": lambda a, N: (4, (N - 512) // 256 + 1, 256)},
     "DenoiseWaveGrad": {"config": None, "batch": 8, "samples": None, "num_samples": False, "launches": None,
                         "dtypes": "bfloat16,float32",
                         "cases": (("WaveGrad", 32100), ("DenoiseWaveGrad1", 32000), ("DenoiseWaveGrad3", 32100))},
@@ -112,14 +121,14 @@ def _family(name):
         mode = re.match(r"I\w*?Li(\d+)E", name[pos:])
         return ident + ("<%s>" % mode.group(1) if mode else "")
     name = re.sub(r"^void\s+", "", name).replace("(anonymous namespace)::", "").replace("sddm::", "")
-    m = re.match(r"(\w+)(?:<[^,>]*,\s*(\d+)>)?", re.sub(r"\(.*$", "", name))
+    m = re.match(r"(\w+)(?:<[^,>]*,\s*(\d+)\s*[,>])?", re.sub(r"\(.*$", "", name))
     return (m.group(1) + ("<%s>" % m.group(2) if m.group(2) else "")) if m else name
 
 
-def kernel_shares(torch, spec, dtype, B, N, n_tstb):
-    """CAUNet: kernel families' shares of one PROFILE_STEPS-step call, and the GRU's time per recurrent step."""
+def kernel_shares(torch, spec, network, dtype, B, N, net_args):
+    """Kernel families' shares of one PROFILE_STEPS-step call, and the GRU's time per recurrent step."""
     from torch.profiler import ProfilerActivity, profile
-    model, _ = _model(torch, spec, "CAUNet", dtype, N, PROFILE_STEPS)
+    model, _ = _model(torch, spec, network, dtype, N, PROFILE_STEPS)
     cond = (0.3 * torch.randn(B, 1, N, device="cuda")).clamp(-1, 1)
     model.infer(cond, seed=1)
     torch.cuda.synchronize()
@@ -136,8 +145,8 @@ def kernel_shares(torch, spec, dtype, B, N, n_tstb):
     total = sum(fam.values())
     if not total:
         raise RuntimeError("torch.profiler recorded no kernels")
-    frames = (N - 128) // 64 + 1
-    recurrent = PROFILE_STEPS * n_tstb * (8 + frames)
+    layers, dim2, dim1 = spec["transformer"](net_args, N)
+    recurrent = PROFILE_STEPS * layers * (dim1 + dim2)
     gru = sum(v for k, v in fam.items() if "gru" in k)
     return ({k: round(v / total, 4) for k, v in sorted(fam.items(), key=lambda kv: -kv[1])},
             gru / recurrent, total / PROFILE_STEPS / 1e3)
@@ -180,9 +189,9 @@ def run_case(torch, spec, network, dtype, B, N, steps, reps, kernels):
         profiled_ops(torch, model, cond, res)
     elif launches is not None:
         res["launches_per_step"] = launches(net_args) if callable(launches) else launches
-    if network == "CAUNet" and kernels:
+    if "transformer" in spec and kernels:
         res["kernel_share"], res["gru_us_per_recurrent_step"], res["kernel_ms_per_step"] = kernel_shares(
-            torch, spec, dtype, B, N, net_args["n_TSTB"])
+            torch, spec, network, dtype, B, N, net_args)
     return res
 
 
@@ -194,7 +203,7 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--dtypes", default=None, help="default: bfloat16,float16,float32 (DenoiseWaveGrad: bfloat16,float32)")
-    ap.add_argument("--no-kernels", action="store_true", help="CAUNet: skip the profiled call")
+    ap.add_argument("--no-kernels", action="store_true", help="CAUNet, TSTNN: skip the profiled call")
     ap.add_argument("--no-unet", action="store_true", help="UNetTST: skip the UNetModified2 cases")
     ap.add_argument("--log", default=None, help="also append the result lines to this file")
     args = ap.parse_args()
