@@ -190,6 +190,17 @@ int sddm_initial_state(sddm_ctx* ctx, int mode, const float* cond, int64_t B, in
 int sddm_schedule(const char* schedule, int n_timestep, double linear_start, double linear_end,
                   float* out);
 
+/* Host-only: the plan of one UNetModified2 / UNetTST reverse step -- which kernel and tiling every
+ * layer gets -- as a JSON list written into buf, one object per step in launch order.  config_json:
+ * a config as sddm_configure takes it ("network", "num_samples", "lane_rows" are read, with the same
+ * checks); tuning_json: a table file as sddm_set_conv_tuning takes it, or NULL.  Every object has the
+ * layer "name" and the step "type"; conv steps carry the kernel family ("strip" | "tile" | "deep" |
+ * "chain"), the geometry (s2, up, Ho, Wo, CA, CB, Cout, RCA, RCB, res, gn), the kernel choice (TR,
+ * TW, tiles_x, n_tiles, tile, mt, nw, nb, nblk, mpi, SR) and, for tile kernels, the configuration's
+ * (wpx, wco, fp, fc).  Needs no context and touches no device. */
+int sddm_unet_plan(const char* config_json, const char* tuning_json, int compute_dtype, char* buf,
+                   int64_t buflen);
+
 /* Timing of the last sddm_sample's dominant kernel class (HIP events on the sampling stream):
  * average duration in ms of the UNet 3x3 convolution launches, and how many were timed. */
 int sddm_profile_enable(sddm_ctx* ctx, int enable);

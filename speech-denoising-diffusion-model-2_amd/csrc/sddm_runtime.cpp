@@ -2,7 +2,8 @@
 // Dual_Transformer's dt_pack) and the C ABI declared in include/sddm_hip.h.  The ABI drives whichever
 // network is configured through Net; every network path is one header:
 //   UNetModified2, UNetTST  unet_runtime.h   the per-batch plan of one reverse step, run in lanes whose
-//                                            step graphs replay concurrently
+//                                            step graphs replay concurrently; unet_plan.h is its planner
+//                                            (host arithmetic only; sddm_unet_plan returns a plan as JSON)
 //   DiffWave             dw_runtime.h  \
 //   WaveGrad, DenoiseWaveGrad1 / 3  wg_runtime.h   >  sequential networks: each implements SeqNet, and
 //   Waveunet3            wu_runtime.h  |   seq_sample / seq_forward here drive whichever is configured
@@ -93,6 +94,8 @@ static void store_elem(void* base, size_t idx, float v, int dt) {
   else if (dt == DT_BF16) ((uint16_t*)base)[idx] = f32_to_bf16_bits(v);
   else ((uint16_t*)base)[idx] = f32_to_f16_bits(v);
 }
+
+#include "unet_plan.h"   // the UNet planner: host arithmetic only (TuneTable is part of the context)
 
 // ---------------------------------------------------------------------------------------------
 // device arena (one hipMalloc, bump allocation, 256-B alignment)
@@ -214,15 +217,7 @@ struct sddm_ctx {
   std::vector<hipEvent_t> ev_pool;
   std::vector<std::pair<int, int>> ev_pend;   // (op index, pool index of the start event)
   std::vector<ProfAcc> op_acc;                // per op index (the same layer list in every lane)
-  // measured per-layer kernel tables (sddm_set_conv_tuning), each valid for one lane batch /
-  // dtype / num_samples: conv_deep tiles per layer name (pixels per block, waves) and the kernel
-  // choice (1 strip, 2 tile (a = configuration), 3 deep (a = pixels, b = waves, c = channels))
-  struct KernTune { int kind, a, b, c; };
-  struct TuneTable {
-    std::map<std::string, std::pair<int, int>> deep_tune;
-    std::map<std::string, KernTune> kern_tune;
-    int B = -1, dtype = -1, N = -1;
-  };
+  // measured per-layer kernel tables (sddm_set_conv_tuning; unet_plan.h)
   std::vector<TuneTable> tunes;
   int hop_samples = 256;
 
@@ -882,55 +877,39 @@ int sddm_q_sample(sddm_ctx* c, int mode, const float* x0, const float* y, const 
 
 int sddm_set_conv_tuning(sddm_ctx* c, const char* json) {
   if (!c || !json) FAIL(SDDM_ERR_INVALID_ARG, "NULL argument");
-  Json j;
-  try {
-    j = Json::parse(json);
-  } catch (const std::exception& e) {
-    FAIL(SDDM_ERR_INVALID_ARG, "tuning JSON: %s", e.what());
-  }
-  // one table, or {"tables": [table, ...]}: the plan takes the first whose lane batch, dtype and
-  // length match it (a bf16 table also serves f16 plans)
-  std::vector<const Json*> tabs;
-  if (j.has("tables")) {
-    const Json& arr = j.at("tables");
-    if (arr.kind != Json::ARR) FAIL(SDDM_ERR_INVALID_ARG, "tables: a list");
-    for (const auto& t : arr.arr) tabs.push_back(&t);
-  } else {
-    tabs.push_back(&j);
-  }
-  std::vector<sddm_ctx::TuneTable> out;
-  for (const Json* tp : tabs) {
-    const Json& t = *tp;
-    if (t.kind != Json::OBJ) FAIL(SDDM_ERR_INVALID_ARG, "tuning table: an object");
-    sddm_ctx::TuneTable tt;
-    const std::string dts = t.string("dtype", "");
-    tt.dtype = dts == "float32" ? DT_F32 : dts == "bfloat16" ? DT_BF16 : dts == "float16" ? DT_F16 : -1;
-    if (t.has("deep"))
-      for (const auto& kv : t.at("deep").obj) {
-        if (kv.second.kind != Json::ARR || kv.second.arr.size() != 2) FAIL(SDDM_ERR_INVALID_ARG, "deep.%s: [mt, nw]", kv.first.c_str());
-        tt.deep_tune[kv.first] = {(int)kv.second.arr[0].num, (int)kv.second.arr[1].num};
-      }
-    // "kernel": {"<layer>": "strip" | "tile:<cfg>" | "deep" | "deep:<mt>:<nw>[:<nb>]" | "chain"}
-    if (t.has("kernel"))
-      for (const auto& kv : t.at("kernel").obj) {
-        if (kv.second.kind != Json::STR) FAIL(SDDM_ERR_INVALID_ARG, "kernel.%s: a string", kv.first.c_str());
-        const std::string& v = kv.second.str;
-        sddm_ctx::KernTune k{0, 0, 0, 0};
-        if (v == "strip") k.kind = 1;
-        else if (v.rfind("tile:", 0) == 0) { k.kind = 2; k.a = std::atoi(v.c_str() + 5); }
-        else if (v == "deep") k.kind = 3;
-        else if (v.rfind("deep:", 0) == 0) { k.kind = 3; std::sscanf(v.c_str() + 5, "%d:%d:%d", &k.a, &k.b, &k.c); }
-        else if (v == "chain") k.kind = 4;
-        else FAIL(SDDM_ERR_INVALID_ARG, "kernel.%s: unknown choice '%s'", kv.first.c_str(), v.c_str());
-        if (k.kind == 2 && (k.a < 0 || k.a >= conv_tile_ncfg())) FAIL(SDDM_ERR_INVALID_ARG, "kernel.%s: tile configuration %d", kv.first.c_str(), k.a);
-        tt.kern_tune[kv.first] = k;
-      }
-    tt.B = (int)t.number("lane_batch", -1);
-    tt.N = (int)t.number("num_samples", -1);
-    out.push_back(std::move(tt));
-  }
+  // the plan takes the first table whose lane batch, dtype and length match it (match_tuning)
+  std::vector<TuneTable> out;
+  TRY(parse_conv_tuning(json, out));
   c->tunes = std::move(out);
   if (c->net) c->net->replan();                     // re-plan on the next call
+  return SDDM_OK;
+}
+
+int sddm_unet_plan(const char* config_json, const char* tuning_json, int compute_dtype, char* buf, int64_t buflen) {
+  if (!config_json || !buf || buflen < 3) FAIL(SDDM_ERR_INVALID_ARG, "NULL argument");
+  if (compute_dtype < 0 || compute_dtype > 2) FAIL(SDDM_ERR_INVALID_ARG, "bad dtype %d", compute_dtype);
+  Json cfg;
+  try {
+    cfg = Json::parse(config_json);
+  } catch (const std::exception& e) {
+    FAIL(SDDM_ERR_INVALID_ARG, "config JSON: %s", e.what());
+  }
+  const Json& net = cfg.at("network");
+  const std::string type = net.string("type", "");
+  if (type != "UNetModified2" && type != "UNetTST") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "network type '%s' has no plan", type.c_str());
+  UNetCfg u;
+  int Ns = -1;
+  TRY(unet_configure(cfg, net.at("args"), type == "UNetTST", u, &Ns));
+  int lane_rows = (int)cfg.number("lane_rows", 16);            // as sddm_create / sddm_configure: SDDM_LANE_ROWS overrides
+  if (const char* lr = std::getenv("SDDM_LANE_ROWS")) lane_rows = std::max(1, std::atoi(lr));
+  if (lane_rows < 1) FAIL(SDDM_ERR_INVALID_ARG, "lane_rows %d", lane_rows);
+  std::vector<TuneTable> tunes;
+  if (tuning_json) TRY(parse_conv_tuning(tuning_json, tunes));
+  UNetPlan plan;
+  TRY(plan_unet(u, Ns, compute_dtype, lane_rows, match_tuning(tunes, lane_rows, Ns, compute_dtype), PlanKnobs::env(), plan));
+  const std::string js = plan_json(plan);
+  if ((int64_t)js.size() + 1 > buflen) FAIL(SDDM_ERR_INVALID_ARG, "buffer too small (%zu)", js.size() + 1);
+  std::memcpy(buf, js.c_str(), js.size() + 1);
   return SDDM_OK;
 }
 

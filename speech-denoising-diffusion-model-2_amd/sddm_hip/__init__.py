@@ -25,7 +25,7 @@ TABLE_NAMES = ("betas", "alphas", "alpha_bar", "sqrt_alpha_bar", "predicted_nois
 EXPORTS = ("sddm_abi_version", "sddm_last_error", "sddm_create", "sddm_destroy", "sddm_configure",
            "sddm_load_param", "sddm_missing_params", "sddm_sample", "sddm_sample_noise", "sddm_sample_continuous",
            "sddm_network_forward", "sddm_dual_transformer",
-           "sddm_transition", "sddm_q_sample", "sddm_log_spectrogram", "sddm_set_conv_tuning", "sddm_initial_state", "sddm_schedule", "sddm_profile_enable",
+           "sddm_transition", "sddm_q_sample", "sddm_log_spectrogram", "sddm_set_conv_tuning", "sddm_initial_state", "sddm_schedule", "sddm_unet_plan", "sddm_profile_enable",
            "sddm_profile_read", "sddm_profile_ops")
 
 _lib = None
@@ -59,6 +59,7 @@ def lib():
         L.sddm_set_conv_tuning.argtypes = [vp, ctypes.c_char_p]
         L.sddm_initial_state.argtypes = [vp, c_int, vp, i64, i64, u64, i64, vp, vp]
         L.sddm_schedule.argtypes = [ctypes.c_char_p, c_int, ctypes.c_double, ctypes.c_double, vp]
+        L.sddm_unet_plan.argtypes = [ctypes.c_char_p, ctypes.c_char_p, c_int, ctypes.c_char_p, i64]
         L.sddm_profile_enable.argtypes = [vp, c_int]
         L.sddm_profile_read.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),
                                         ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_double),
@@ -95,6 +96,24 @@ def schedule(schedule="linear", n_timestep=1000, linear_start=1e-4, linear_end=2
     check(lib().sddm_schedule(str(schedule).encode(), int(n_timestep), float(linear_start),
                               float(linear_end), out.ctypes.data))
     return dict(zip(TABLE_NAMES, out))
+
+
+def unet_plan(cfg, tuning_text=None, dtype="bfloat16"):
+    """The plan of one UNetModified2 / UNetTST step (host computation in the library, no GPU needed):
+    a list with one dict per step in launch order; conv steps carry the kernel family, the geometry
+    and the kernel choice (sddm_unet_plan).  cfg: a config dict as Context takes it (its "network",
+    "num_samples" and "lane_rows" are read); tuning_text: the text of a tuning file, or None."""
+    buf = ctypes.create_string_buffer(1 << 20)
+    check(lib().sddm_unet_plan(json.dumps(cfg).encode(), None if tuning_text is None else tuning_text.encode(),
+                               DTYPES[str(dtype)], buf, len(buf)))
+    return json.loads(buf.value.decode())
+
+
+def planned_kernel(step):
+    """A conv step of unet_plan in the tuning table's vocabulary: "strip" | "tile:<cfg>" |
+    "deep:<mt>:<nw>:<nb>" | "chain"."""
+    k = step["kernel"]
+    return {"tile": f"tile:{step['tile']}", "deep": f"deep:{step['mt']}:{step['nw']}:{step['nb']}"}.get(k, k)
 
 
 def _ptr(t):

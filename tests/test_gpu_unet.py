@@ -332,6 +332,36 @@ def test_unet_forward_small_lane_measured_table(torch_cuda, lane):
     assert np.isfinite(eps).all() and max(errs) <= 2.5e-2
 
 
+@pytest.mark.parametrize("N,B,lane", [(2112, 2, None), (16448, 4, 4)])
+def test_plan_call_agrees_with_the_run(torch_cuda, N, B, lane):
+    """sddm_hip.unet_plan (the planner without a device, pinned on the CPU by test_unet_plan.py) names
+    the kernels a context runs: the heuristic's at N=2112, the repository's measured table's at
+    N=16448 in lanes of 4."""
+    cfg = unet_config(N)
+    text = None
+    if lane:
+        cfg["lane_rows"] = lane
+        text, tab = repo_tuning_table(N, lane)
+        assert tab is not None
+    ctx = sddm_hip.Context(cfg, 0, "bfloat16")
+    for k, v in unet_params(N).items():
+        ctx.load_param("noise_estimate_model." + k, v)
+    if text:
+        ctx.set_conv_tuning(text)
+    ctx.profile(True)
+    dev = torch_cuda.device("cuda", 0)
+    x = torch_cuda.randn((B, 1, N), device=dev, generator=torch_cuda.Generator(dev).manual_seed(3))
+    eps = torch_cuda.full((B, 1, N), float("nan"), device=dev)
+    ctx.network_forward(x, x * 0.5, torch_cuda.full((B,), 0.7, device=dev), eps)
+    torch_cuda.cuda.synchronize()
+    ran = planned_kernels(ctx)
+    ctx.profile(False)
+    assert torch_cuda.isfinite(eps).all()
+    plan = sddm_hip.unet_plan(cfg, text, "bfloat16")
+    want = {s["name"]: sddm_hip.planned_kernel(s) for s in plan if s["type"] == "conv"}
+    assert len(want) == 42 and ran == want
+
+
 _CONFIG5_ROWS = {}
 
 

@@ -17,8 +17,8 @@ import gen_shapes as G  # noqa: E402
 
 
 def main():
-    net = json.load(open(G.NETCFG))["network"]["args"]
-    tabs = json.load(open(G.TUNING))["tables"]
+    tuning_text = open(G.TUNING).read()
+    tabs = json.loads(tuning_text)["tables"]
     t = [x for x in tabs if x["num_samples"] == 16448 and x["lane_batch"] == 16][0]
     us = {}
     if len(sys.argv) > 1:
@@ -26,15 +26,10 @@ def main():
             us[o["name"].split("[")[0]] = o["avg_ms"] * 1e3
     print(f"{'layer':16s} {'cfg':>4s} {'tile':>7s} {'NB':>3s} {'Cout/NB':>7s} {'halo':>5s} {'ratio':>6s} {'min':>5s} {'us':>6s}")
     tot = 0.0
-    for c in G.convs(net, t["num_samples"]):
-        k = t["kernel"].get(c["name"], "")
-        if not k.startswith("tile:"):
+    for c in G.planned_convs(t, tuning_text):      # the runtime's own plan of the headline geometry
+        if c["kernel"] != "tile":
             continue
-        cfg = int(k[5:])
-        wpx, wco, fp, fc = G.TILE_CFGS[cfg]
-        MT, NB = wpx * fp * 16, wco * fc * 16
-        TW = min(c["Wo"], MT)
-        TR = min(MT // TW, c["Ho"])
+        cfg, TR, TW, NB = c["tile"], c["TR"], c["TW"], c["wco"] * c["fc"] * 16
         halo = (2 * TR + 1) * (2 * TW + 1) if c["s2"] else (TR + 2) * (TW + 2)
         nblk = -(-c["Cout"] // NB)
         ratio = halo * nblk / (TR * TW)
