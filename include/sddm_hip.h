@@ -60,7 +60,7 @@ void sddm_destroy(sddm_ctx* ctx);
  * parse_config.py:82-95).  `json` is {"arch": {...}, "diffusion": {...}, "network": {...},
  * "num_samples": N} with the reference's type names and args verbatim
  * (config_unet.json, config_diffwave.json, config_wavegrad.json, and the default config.json).
- * Network types: UNetModified2, UNetTST, CAUNet, TSTNN, DenoiseWaveGrad1, DenoiseWaveGrad3, Waveunet,
+ * Network types: UNetModified2, UNetTST, UNetModified, CAUNet, TSTNN, DenoiseWaveGrad1, DenoiseWaveGrad3, Waveunet,
  * Waveunet2 and Waveunet3 under arch SDDM
  * (with its p_transition / noise_condition args); DiffWave and WaveGrad under arch
  * SDDM_spectrogram.  Any other pairing or type (DenoiseWaveGrad2 among them) returns
@@ -81,7 +81,12 @@ void sddm_destroy(sddm_ctx* ctx);
  * n_TSTB >= 1 and use_affine_level false or true, and refuses any other value of them, naming the
  * argument; it needs no num_samples.  TSTNN (config_tstnn.json) is built for F 512, stride 256 and
  * n_channels 64 and refuses any other value of them, naming the argument; it needs no num_samples and
- * never reads the noise level.  A context around a stand-alone block may add num_layers >= 1 (the
+ * never reads the noise level.  UNetModified (config_unetmodified.json; the SR3-style U-Net with
+ * spatial self-attention, model/UNetModified.py:192-323) takes UNetModified2's arguments and attn_layer,
+ * a list of levels (an int, the reference class's default, is refused with SDDM_ERR_INVALID_ARG as the
+ * reference raises TypeError); it needs inner_channel 32, a segment_len dividing 512, frames and
+ * segment_len multiples of 2^(levels - 1), at most 256 channels wherever an attention sits, and refuses
+ * with_noise_level_emb false.  A context around a stand-alone block may add num_layers >= 1 (the
  * network's own Dual_Transformer has 4).  The 1-D networks need no num_samples: they take any positive
  * multiple of their hop (see sddm_sample). */
 int sddm_configure(sddm_ctx* ctx, const char* json);
@@ -147,6 +152,17 @@ int sddm_network_forward(sddm_ctx* ctx, const float* cond, const float* x_t,
 int sddm_dual_transformer(sddm_ctx* ctx, const float* in, int64_t B, int64_t dim2, int64_t dim1,
                           float* out, void* stream);
 
+/* Replaces one SelfAttention.forward(input) call (model/UNetModified.py:150-169: GroupNorm, 1x1 qkv conv,
+ * softmax(Q K^T / sqrt(C)) V over all H * W positions with one head, 1x1 out conv, + input) on a context
+ * configured for network UNetModified: layer_name is the attention's state-dict prefix without
+ * noise_estimate_model. ("mid.0.attn", "downs.5.attn", ...), in and out are [B, C, H, W] fp32 device
+ * (NCHW, as the reference module takes it) with C the layer's channels.  Only the layer's own parameters
+ * need to be loaded.  The block runs in the context's compute dtype, so in a 16-bit context the input
+ * and the output are rounded to it.  Any H * W with B * H * W up to 2^24.  Returns after the result is
+ * complete. */
+int sddm_self_attention(sddm_ctx* ctx, const char* layer_name, const float* in, int64_t B, int64_t H,
+                        int64_t W, float* out, void* stream);
+
 /* Replaces diffusion.p_transition*(x_t, t, predicted[, condition]) (diffusion.py:164-223).
  * cond may be NULL for modes that do not read it. */
 int sddm_transition(sddm_ctx* ctx, int mode, const float* x_t, const float* eps,
@@ -190,12 +206,13 @@ int sddm_initial_state(sddm_ctx* ctx, int mode, const float* cond, int64_t B, in
 int sddm_schedule(const char* schedule, int n_timestep, double linear_start, double linear_end,
                   float* out);
 
-/* Host-only: the plan of one UNetModified2 / UNetTST reverse step -- which kernel and tiling every
+/* Host-only: the plan of one UNetModified2 / UNetTST / UNetModified reverse step -- which kernel and tiling every
  * layer gets -- as a JSON list written into buf, one object per step in launch order.  config_json:
  * a config as sddm_configure takes it ("network", "num_samples", "lane_rows" are read, with the same
  * checks); tuning_json: a table file as sddm_set_conv_tuning takes it, or NULL.  Every object has the
- * layer "name" and the step "type"; conv steps carry the kernel family ("strip" | "tile" | "deep" |
- * "chain"), the geometry (s2, up, Ho, Wo, CA, CB, Cout, RCA, RCB, res, gn), the kernel choice (TR,
+ * layer "name" and the step "type" (a SelfAttention is one step of type "attention" named
+ * "<layer>.attn", with P, C, the query tile QT and the key tile); conv steps carry the kernel family
+ * ("strip" | "tile" | "deep" | "chain" | "wide"), the geometry (s2, up, Ho, Wo, CA, CB, Cout, RCA, RCB, res, gn), the kernel choice (TR,
  * TW, tiles_x, n_tiles, tile, mt, nw, nb, nblk, mpi, SR) and, for tile kernels, the configuration's
  * (wpx, wco, fp, fc).  Needs no context and touches no device. */
 int sddm_unet_plan(const char* config_json, const char* tuning_json, int compute_dtype, char* buf,

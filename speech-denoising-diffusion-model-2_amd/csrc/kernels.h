@@ -127,6 +127,11 @@ hipError_t launch_conv_deep(int dtype, int mt, bool s2, const ConvArgs& a, int B
 size_t conv_deep_lds_bytes(int dtype, int mt, bool s2, const ConvArgs& a);
 int conv_deep_ring_depth(int dtype, int mt, int nw, int ksteps, int nb);   // the D template argument (profiles)
 
+// ---- K-chunked 3x3 convolution for the layers neither kernel above holds (conv_wide.hip): the halo of
+// 32 input channels at a time, so its LDS does not grow with the channels.  Tiles of at most 64 pixels
+hipError_t launch_conv_wide(int dtype, bool s2, const ConvArgs& a, int B, hipStream_t s);
+size_t conv_wide_lds_bytes(int dtype, bool s2, const ConvArgs& a);
+
 // LDS per workgroup every launcher and planner sizes against: gfx950's 160 KiB (sddm_create fails
 // on a device that offers less, so no plan is built for LDS the device does not have)
 constexpr int kLdsBytes = 160 * 1024;

@@ -1,7 +1,7 @@
 // libsddm_hip runtime: context, parameter registry, weight packers (WeightPacker, store_frags, the
 // Dual_Transformer's dt_pack) and the C ABI declared in include/sddm_hip.h.  The ABI drives whichever
 // network is configured through Net; every network path is one header:
-//   UNetModified2, UNetTST  unet_runtime.h   the per-batch plan of one reverse step, run in lanes whose
+//   UNetModified2, UNetTST, UNetModified  unet_runtime.h   the per-batch plan of one reverse step, run in lanes whose
 //                                            step graphs replay concurrently; unet_plan.h is its planner
 //                                            (host arithmetic only; sddm_unet_plan returns a plan as JSON)
 //   DiffWave             dw_runtime.h  \
@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
@@ -692,12 +693,13 @@ int sddm_configure(sddm_ctx* c, const char* json) {
     return finish_configure(c, T, tabs, shapes, std::move(us), -1);
   }
   // UNetTST (UNetTST.py:270-392): UNetModified2 with mid = Dual_Transformer and no final Swish in the noise MLP
-  const bool tst = c->net_type == "UNetTST";
-  if (c->net_type != "UNetModified2" && !tst) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "network type '%s'", c->net_type.c_str());
+  // UNetModified (UNetModified.py:192-323): the SR3-style U-Net with SelfAttention at the levels of attn_layer
+  const bool tst = c->net_type == "UNetTST", modified = c->net_type == "UNetModified";
+  if (c->net_type != "UNetModified2" && !tst && !modified) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "network type '%s'", c->net_type.c_str());
   if (c->arch_type != "SDDM") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "%s under arch '%s'", c->net_type.c_str(), c->arch_type.c_str());
   auto us = std::make_unique<UNetState>();
   int Ns = -1;
-  TRY(unet_configure(cfg, net.at("args"), tst, us->u, &Ns));
+  TRY(unet_configure(cfg, net.at("args"), tst, us->u, &Ns, modified));
   const auto shapes = unet_param_shapes(us->u);
   return finish_configure(c, T, tabs, shapes, std::move(us), Ns);
 }
@@ -843,6 +845,56 @@ int sddm_dual_transformer(sddm_ctx* c, const float* in, int64_t B, int64_t dim2,
   return SDDM_OK;
 }
 
+// One SelfAttention of a UNetModified context alone (UNetModified.py:150-169).  Only the layer's own
+// parameters need to be loaded: parameters outside it that are still missing are packed as zeros
+int sddm_self_attention(sddm_ctx* c, const char* layer, const float* in, int64_t B, int64_t H, int64_t W, float* out,
+                        void* stream) {
+  if (!c || !c->configured) FAIL(SDDM_ERR_STATE, "context not configured");
+  if (c->net_type != "UNetModified") FAIL(SDDM_ERR_STATE, "sddm_self_attention needs a context configured for UNetModified");
+  if (!layer || !in || !out) FAIL(SDDM_ERR_INVALID_ARG, "NULL argument");
+  const std::string blk = layer;
+  const auto it = c->params.find(blk + ".qkv.weight");
+  if (it == c->params.end()) FAIL(SDDM_ERR_INVALID_ARG, "the network has no attention layer '%s'", layer);
+  const int C = (int)it->second.shape[1];
+  if (B < 1 || B > 65535 || H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20) || B * H * W > ((int64_t)1 << 24))
+    FAIL(SDDM_ERR_SHAPE, "B=%lld H=%lld W=%lld: the attention kernels index B * H * W up to 2^24", (long long)B, (long long)H, (long long)W);
+  SDDM_HIP_CHECK(hipSetDevice(c->device));
+  for (auto& kv : c->params) {
+    if (kv.second.loaded) continue;
+    if (kv.first.rfind(blk + ".", 0) == 0) FAIL(SDDM_ERR_STATE, "parameter %s not loaded", kv.first.c_str());
+    int64_t n = 1;
+    for (int64_t d : kv.second.shape) n *= d;
+    if ((int64_t)kv.second.data.size() != n) kv.second.data.assign((size_t)n, 0.f);
+  }
+  if (c->params_dirty) TRY(c->net->upload_weights(c));
+  if (c->tables_dirty) TRY(upload_tables(c));
+  const UNetState& n = static_cast<const UNetState&>(*c->net);
+  hipStream_t s = (hipStream_t)stream;
+  const int P = (int)(H * W), QT = attn_query_tile(P);
+  if (attn_core_lds_bytes(c->dtype, C) > (size_t)kLdsBytes) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "%s: %d channels", layer, C);
+  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t act = al((size_t)B * P * C * dtype_size(c->dtype)), st = al(sizeof(float) * (size_t)B * (P / QT) * C * 2);
+  char* buf = nullptr;
+  SDDM_HIP_CHECK(hipMalloc(&buf, 5 * act + st));       // x, out, qkv (3), the input's statistics
+  AttnArgs a{};
+  a.x = buf; a.out = buf + act; a.qkv = buf + 2 * act; a.gst = (const float*)(buf + 5 * act); a.gtiles = P / QT; a.gntile = QT;
+  a.gamma = c->warena.at<float>(n.woff.at(blk + ".norm.gamma")); a.beta = c->warena.at<float>(n.woff.at(blk + ".norm.beta"));
+  a.groups = n.u.groups; a.eps = 1e-5f;
+  a.wqkv_f = c->warena.base + n.woff.at(blk + ".qkv_f"); a.wout_f = c->warena.base + n.woff.at(blk + ".out_f");
+  a.bout = c->warena.at<float>(n.woff.at(blk + ".out.b"));
+  a.stats = nullptr; a.P = P; a.C = C; a.QT = QT;
+  a.scale_log2 = (float)(1.4426950408889634 / std::sqrt((double)C));
+  hipError_t e = launch_dt_pack(c->dtype, in, buf, (int)B, C, P, s);
+  if (e == hipSuccess) e = launch_attn_input_stats(c->dtype, buf, (float*)(buf + 5 * act), (int)B, P, C, QT, s);
+  if (e == hipSuccess) e = launch_attn_qkv(c->dtype, a, (int)B, s);
+  if (e == hipSuccess) e = launch_attn_core(c->dtype, a, (int)B, s);
+  if (e == hipSuccess) e = launch_dt_unpack(c->dtype, buf + act, out, (int)B, C, P, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(buf);
+  if (e != hipSuccess) FAIL(SDDM_ERR_HIP, "self_attention: %s", hipGetErrorString(e));
+  return SDDM_OK;
+}
+
 int sddm_transition(sddm_ctx* c, int mode, const float* x_t, const float* eps, const float* cond, int t, int64_t B,
                     int64_t N, uint64_t seed, int64_t row_offset, float* out, void* stream) {
   if (!c || !c->configured) FAIL(SDDM_ERR_STATE, "context not configured");
@@ -896,10 +948,11 @@ int sddm_unet_plan(const char* config_json, const char* tuning_json, int compute
   }
   const Json& net = cfg.at("network");
   const std::string type = net.string("type", "");
-  if (type != "UNetModified2" && type != "UNetTST") FAIL(SDDM_ERR_NOT_IMPLEMENTED, "network type '%s' has no plan", type.c_str());
+  if (type != "UNetModified2" && type != "UNetTST" && type != "UNetModified")
+    FAIL(SDDM_ERR_NOT_IMPLEMENTED, "network type '%s' has no plan", type.c_str());
   UNetCfg u;
   int Ns = -1;
-  TRY(unet_configure(cfg, net.at("args"), type == "UNetTST", u, &Ns));
+  TRY(unet_configure(cfg, net.at("args"), type == "UNetTST", u, &Ns, type == "UNetModified"));
   int lane_rows = (int)cfg.number("lane_rows", 16);            // as sddm_create / sddm_configure: SDDM_LANE_ROWS overrides
   if (const char* lr = std::getenv("SDDM_LANE_ROWS")) lane_rows = std::max(1, std::atoi(lr));
   if (lane_rows < 1) FAIL(SDDM_ERR_INVALID_ARG, "lane_rows %d", lane_rows);

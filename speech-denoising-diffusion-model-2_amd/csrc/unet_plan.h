@@ -8,6 +8,7 @@
 #pragma once
 #include "kernels.h"
 #include "dual_transformer.h"
+#include "self_attention.h"
 
 // ---------------------------------------------------------------------------------------------
 // UNetModified2 architecture (UNetModified2.py:146-235)
@@ -19,14 +20,59 @@ struct UNetCfg {
   double dropout = 0.0;
   int mid_tst = 0;   // 1: UNetTST -- mid is Dual_Transformer(C, C, 0, n_tstb) (UNetTST.py:324), and the
   int n_tstb = 6;    //    noise MLP has no final Swish (UNetTST.py:293-298)
+  int modified = 0;  // 1: UNetModified (UNetModified.py:192-323) -- SelfAttention after the ResnetBlocks of the levels in
+  std::vector<int> attn;   // attn_layer, no Downsample after the last level, mid = (block + attention, block),
+                           // res_blocks + 1 decoder blocks per level, Upsample after them; no final Swish in the noise MLP
 };
-struct LayerDesc { int kind; std::string name; int cin, cout; };  // kind 0 conv,1 res,2 down,3 up,4 final,5 dual transformer
+// kind 0 conv,1 res,2 down,3 up,4 final,5 dual transformer; attn: the SelfAttention that follows a res block ("": none)
+struct LayerDesc { int kind; std::string name; int cin, cout; std::string attn = ""; };
+// UNetModified.py:237-277: blocks are ResnetBlocWithAttn, so a block's tensors sit under <layer>.res_block / <layer>.attn
+static void unet_modified_layers(const UNetCfg& c, std::vector<LayerDesc>& downs, std::vector<LayerDesc>& mid,
+                                 std::vector<LayerDesc>& ups, int* last) {
+  auto with_attn = [&](int ind) { return std::find(c.attn.begin(), c.attn.end(), ind) != c.attn.end(); };
+  auto block = [](const char* part, int idx, int cin, int cout, bool attn) {
+    const std::string n = std::string(part) + "." + std::to_string(idx);
+    return LayerDesc{1, n + ".res_block", cin, cout, attn ? n + ".attn" : ""};
+  };
+  downs.push_back({0, "downs.0", c.in_channel, c.inner});
+  std::vector<int> feat{c.inner};
+  int cin = c.inner, idx = 1;
+  const int nm = (int)c.mults.size();
+  for (int ind = 0; ind < nm; ++ind) {
+    const int cout = c.inner * c.mults[ind];
+    for (int r = 0; r < c.res_blocks; ++r) {
+      downs.push_back(block("downs", idx++, cin, cout, with_attn(ind)));
+      feat.push_back(cout);
+      cin = cout;
+    }
+    if (ind != nm - 1) {
+      downs.push_back({2, "downs." + std::to_string(idx++), cin, cin});
+      feat.push_back(cin);
+    }
+  }
+  mid.push_back(block("mid", 0, cin, cin, true));
+  mid.push_back(block("mid", 1, cin, cin, false));
+  idx = 0;
+  for (int ind = nm - 1; ind >= 0; --ind) {
+    const int cout = c.inner * c.mults[ind];
+    for (int r = 0; r < c.res_blocks + 1; ++r) {
+      ups.push_back(block("ups", idx++, cin + feat.back(), cout, with_attn(ind)));
+      feat.pop_back();
+      cin = cout;
+    }
+    if (ind >= 1) ups.push_back({3, "ups." + std::to_string(idx++), cin, cin});
+  }
+  *last = cin;
+}
 static std::vector<LayerDesc> unet_layers(const UNetCfg& c, std::vector<LayerDesc>* downs_out,
                                           std::vector<LayerDesc>* mid_out, std::vector<LayerDesc>* ups_out) {
   std::vector<LayerDesc> downs, mid, ups;
+  int cin = c.inner, idx = 1, cout = c.inner;
+  if (c.modified) {
+    unet_modified_layers(c, downs, mid, ups, &cout);
+  } else {
   downs.push_back({0, "downs.0", c.in_channel, c.inner});
   std::vector<int> feat{c.inner};
-  int cin = c.inner, idx = 1, cout = c.inner;
   for (size_t ind = 0; ind < c.mults.size(); ++ind) {
     cout = c.inner * c.mults[ind];
     for (int r = 0; r < c.res_blocks; ++r) {
@@ -52,6 +98,7 @@ static std::vector<LayerDesc> unet_layers(const UNetCfg& c, std::vector<LayerDes
       feat.pop_back();
       cin = cout;
     }
+  }
   }
   std::vector<LayerDesc> all;
   all.insert(all.end(), downs.begin(), downs.end());
@@ -179,6 +226,7 @@ struct ConvChoice {
   int tile = -1;                                  // conv_tile configuration (16-bit dtypes), -1: none
   int TR = 0, TW = 0, tiles_x = 0, n_tiles = 0;  // stats tiling of the output
   int chain = 0;                                  // 1: part of the bottom-level chain launch (conv_chain.hip)
+  int wide = 0;                                   // 1: K-chunked kernel (conv_wide.hip): mt = pixels per block
 };
 
 // conv_deep tile (pixels per block) and waves per block.  A block's time is dominated by its
@@ -288,6 +336,24 @@ static bool choose_tile(const PlanKnobs& k, int dt, int B, ConvArgs a, bool s2, 
   return true;
 }
 
+// conv_wide tile: the layers whose K no other kernel holds (float32 from about 256 input channels plus a
+// res_conv).  The largest tile of at most 64 pixels whose rows divide the image; untuned
+static bool choose_wide(int dt, ConvArgs a, bool s2, ConvChoice& ch) {
+  if (a.Cout % 32 || (a.CA + a.CB) % 32) return false;
+  for (int mt : {64, 32, 16}) {
+    const int TW = std::min(a.Wo, mt);
+    if (mt % TW || a.Wo % TW) continue;
+    int TR = std::min(mt / TW, a.Ho);
+    while (a.Ho % TR) --TR;
+    a.TR = TR; a.TW = TW; a.tiles_x = a.Wo / TW; a.n_tiles = a.tiles_x * (a.Ho / TR);
+    if (conv_wide_lds_bytes(dt, s2, a) > (size_t)kLdsBytes) continue;
+    ch.strip = 0; ch.tile = -1; ch.wide = 1; ch.mt = TR * TW; ch.nw = 4; ch.nb = 32;
+    ch.TR = TR; ch.TW = TW; ch.tiles_x = a.tiles_x; ch.n_tiles = a.n_tiles;
+    return true;
+  }
+  return false;
+}
+
 static bool choose_conv(const PlanKnobs& k, int dt, int B, int Cin, int RC, int res_mode, int Ho, int Wo, int Cout, bool s2,
                         bool up, ConvChoice& ch, int want_mt = 0, int want_nw = 0, int kind = 0, int ka = 0, int want_nb = 0) {
   ConvArgs a{};
@@ -298,7 +364,9 @@ static bool choose_conv(const PlanKnobs& k, int dt, int B, int Cin, int RC, int 
     ConvChoice t = ch;
     if (choose_tile(k, dt, B, a, s2, t, ka) && t.tile == ka) { ch = t; return true; }
   }
-  if (!s2 && (Wo == 128 || Wo == 64) && !k.no_strip && (kind == 0 || kind == 1)) {
+  // (the strip kernel holds a res_conv of at most 128 input channels in registers: launch_conv_strip refuses more)
+  const bool strip_res_ok = res_mode != 2 || RC <= 128;
+  if (!s2 && (Wo == 128 || Wo == 64) && !k.no_strip && (kind == 0 || kind == 1) && strip_res_ok) {
     const int nbs[2] = {(Cout % 64 == 0) ? 64 : 32, 32};
     for (int mpi : {256, 128}) {
       if (k.strip_mpi && mpi != k.strip_mpi) continue;
@@ -324,7 +392,8 @@ static bool choose_conv(const PlanKnobs& k, int dt, int B, int Cin, int RC, int 
     }
   }
   if (want_mt == 0 && kind != 3 && choose_tile(k, dt, B, a, s2, ch)) return true;
-  return choose_deep(k, dt, B, a, s2, ch, want_mt, want_nw, want_nb);
+  if (choose_deep(k, dt, B, a, s2, ch, want_mt, want_nw, want_nb)) return true;
+  return choose_wide(dt, a, s2, ch);   // only where nothing above fits: no earlier plan changes
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -332,7 +401,7 @@ static bool choose_conv(const PlanKnobs& k, int dt, int B, int Cin, int RC, int 
 // ---------------------------------------------------------------------------------------------
 struct PlanTensor { int C = 0, H = 0, W = 0, tiles = 0, n_tile = 0; };   // an activation and its per-tile GroupNorm statistics
 struct PlanGN { int a, b; std::string w; };   // GroupNorm sources (finalized in the consumer), `w`: whose gamma / beta
-enum { ST_CONVIN, ST_CONV, ST_FINAL, ST_TST, ST_CAT };
+enum { ST_CONVIN, ST_CONV, ST_FINAL, ST_TST, ST_CAT, ST_ATTN };
 struct Step {
   int type = 0;
   std::string w;          // weight-name prefix
@@ -342,6 +411,7 @@ struct Step {
   bool temb = false;
   ConvChoice ch;
   int TRin = 0, FT = 0;   // ST_CONVIN: frame rows per block; ST_FINAL: frames per block
+  int scratch = -1;       // ST_ATTN: the qkv tensor [P][3C] (no statistics)
 };
 struct UNetPlan {
   int N = 0, F = 0, dt = 0, PB = 0;    // length, frames, dtype, the lane capacity the kernels are chosen for
@@ -417,6 +487,23 @@ struct UNetPlanner {
       st.cout = cout; st.res_mode = cin != cout ? 2 : 1; st.rawA = xa; st.rawB = xb; st.ch = c2; p.steps.push_back(st); }
     return o;
   }
+  // SelfAttention `n` (UNetModified.py:140-169) over tensor x: two launches (attn_qkv, attn_core) in one step;
+  // the output's statistics tiles are the query tiles
+  int attention(const std::string& n, int x) {
+    const PlanTensor t = p.tensors[x];
+    const int P = t.H * t.W, QT = attn_query_tile(P);
+    const int qkv = new_tensor(3 * t.C, t.H, t.W, 0, 0);
+    const int o = new_tensor(t.C, t.H, t.W, P / QT, QT);
+    Step st; st.type = ST_ATTN; st.w = n; st.srcA = x; st.gn = new_gn(x, -1, n + ".norm"); st.scratch = qkv; st.out = o;
+    st.cout = t.C;
+    p.steps.push_back(st);
+    return o;
+  }
+  // a ResnetBlock and the SelfAttention behind it, if the layer has one
+  int block(const LayerDesc& L, int xa, int xb) {
+    const int o = res_block(L.name, xa, xb, L.cin, L.cout);
+    return o < 0 || L.attn.empty() ? o : attention(L.attn, o);
+  }
   // Downsample (3x3, stride 2) or Upsample (nearest x2, then 3x3) of tensor `cur`, which becomes the output
   int resample(const LayerDesc& L, int& cur, bool up) {
     const PlanTensor t = p.tensors[cur];
@@ -443,7 +530,7 @@ struct UNetPlanner {
     for (size_t i = 1; i < downs.size(); ++i) {
       const LayerDesc& L = downs[i];
       if (L.kind == 1) {
-        cur = res_block(L.name, cur, -1, L.cin, L.cout);
+        cur = block(L, cur, -1);
       } else {
         if (p.tensors[cur].H % 2 || p.tensors[cur].W % 2) FAIL(SDDM_ERR_SHAPE, "odd size before %s", L.name.c_str());
         TRY(resample(L, cur, false));
@@ -463,7 +550,7 @@ struct UNetPlanner {
         cur = o;
         continue;
       }
-      cur = res_block(L.name, cur, -1, L.cin, L.cout);
+      cur = block(L, cur, -1);
       if (cur < 0) FAIL(SDDM_ERR_SHAPE, "no tile for %s", L.name.c_str());
     }
     for (const LayerDesc& L : ups) {
@@ -472,7 +559,7 @@ struct UNetPlanner {
         feats.pop_back();
         if (p.tensors[skip].H != p.tensors[cur].H || p.tensors[skip].W != p.tensors[cur].W)
           FAIL(SDDM_ERR_SHAPE, "skip/upsample size mismatch at %s (torch.cat would raise)", L.name.c_str());
-        cur = res_block(L.name, cur, skip, L.cin, L.cout);
+        cur = block(L, cur, skip);
         if (cur < 0) FAIL(SDDM_ERR_SHAPE, "no tile for %s", L.name.c_str());
       } else {
         TRY(resample(L, cur, true));
@@ -495,7 +582,8 @@ static int plan_unet(const UNetCfg& u, int num_samples, int dt, int lane_rows, c
   out = UNetPlan{};
   out.N = num_samples; out.dt = dt; out.PB = std::max(1, lane_rows); out.knobs = k;
   out.F = (num_samples - u.seg) / u.stride + 1;
-  UNetPlanner w{u, tuned, k, out};
+  // (UNetModified: the measured tables name UNetModified2's layers, whose names mean other layers here)
+  UNetPlanner w{u, u.modified ? nullptr : tuned, k, out};
   return w.walk();
 }
 
@@ -524,7 +612,11 @@ static ConvNames conv_names(int dt, bool s2, const ConvChoice& ch, const ConvArg
   const int Cin = a.CA + a.CB;
   char kn[160], ki[192];
   std::string tag;
-  if (ch.chain) {
+  if (ch.wide) {
+    tag = "[wide" + std::to_string(ch.mt) + "]";
+    snprintf(kn, sizeof(kn), "conv_wide_kernel<%s,%d>", dt_name(dt), s2 ? 1 : 0);
+    snprintf(ki, sizeof(ki), "%s", kn);
+  } else if (ch.chain) {
     tag = "[chain]";
     snprintf(kn, sizeof(kn), "conv_chain_kernel<%s,%d,%d,%d>", dt_name(dt), a.Cout, a.Ho, a.Wo);
     snprintf(ki, sizeof(ki), "%s", kn);
@@ -552,7 +644,7 @@ static ConvNames conv_names(int dt, bool s2, const ConvChoice& ch, const ConvArg
 // layer `name`, the step `type` and, where the step writes one, its `out` tensor with the GroupNorm
 // statistics tiling; conv steps carry the kernel family, the geometry and the whole ConvChoice
 static std::string plan_json(const UNetPlan& p) {
-  static const char* kTypes[] = {"conv_in", "conv", "final", "dual_transformer", "concat"};
+  static const char* kTypes[] = {"conv_in", "conv", "final", "dual_transformer", "concat", "attention"};
   std::string js = "[";
   char tmp[1024];
   for (size_t i = 0; i < p.steps.size(); ++i) {
@@ -567,6 +659,11 @@ static std::string plan_json(const UNetPlan& p) {
     }
     if (st.type == ST_CONVIN) { snprintf(tmp, sizeof(tmp), ", \"TR\": %d", st.TRin); js += tmp; }
     if (st.type == ST_FINAL) { snprintf(tmp, sizeof(tmp), ", \"FT\": %d", st.FT); js += tmp; }
+    if (st.type == ST_ATTN) {
+      const PlanTensor& o = p.tensors[st.out];
+      snprintf(tmp, sizeof(tmp), ", \"P\": %d, \"C\": %d, \"QT\": %d, \"key_tile\": %d", o.H * o.W, o.C, o.n_tile, kAttnKeyTile);
+      js += tmp;
+    }
     if (st.type == ST_CONV) {
       const ConvChoice& ch = st.ch;
       const ConvArgs a = conv_geometry(p, st);
@@ -574,7 +671,7 @@ static std::string plan_json(const UNetPlan& p) {
                ", \"kernel\": \"%s\", \"s2\": %d, \"up\": %d, \"Ho\": %d, \"Wo\": %d, \"CA\": %d, \"CB\": %d, \"Cout\": %d, "
                "\"RCA\": %d, \"RCB\": %d, \"res\": %d, \"gn\": %d, \"TR\": %d, \"TW\": %d, \"tiles_x\": %d, \"n_tiles\": %d, "
                "\"tile\": %d, \"mt\": %d, \"nw\": %d, \"nb\": %d, \"nblk\": %d, \"mpi\": %d, \"SR\": %d",
-               ch.chain ? "chain" : ch.strip ? "strip" : ch.tile >= 0 ? "tile" : "deep", st.s2, st.up, a.Ho, a.Wo, a.CA, a.CB,
+               ch.wide ? "wide" : ch.chain ? "chain" : ch.strip ? "strip" : ch.tile >= 0 ? "tile" : "deep", st.s2, st.up, a.Ho, a.Wo, a.CA, a.CB,
                a.Cout, a.RCA, a.RCB, a.res_mode, st.gn >= 0 ? 1 : 0, ch.TR, ch.TW, ch.tiles_x, ch.n_tiles, ch.tile, ch.mt, ch.nw,
                ch.nb, ch.nblk, ch.mpi, ch.SR);
       js += tmp;

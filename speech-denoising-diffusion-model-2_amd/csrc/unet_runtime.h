@@ -28,12 +28,14 @@
 // the network's arguments (`na`; num_samples may also stand at the config's top level) -> `u` and the
 // length the network is built for.  tst: UNetTST (UNetTST.py:270-392), i.e. UNetModified2 with mid =
 // Dual_Transformer and no final Swish in the noise MLP
-static int unet_configure(const Json& cfg, const Json& na, bool tst, UNetCfg& u, int* num_samples) {
+static int unet_configure(const Json& cfg, const Json& na, bool tst, UNetCfg& u, int* num_samples, bool modified = false) {
+  // UNetModified (UNetModified.py:192-323): its own default widths, attention levels, one level boundary fewer
+  u.modified = modified ? 1 : 0;
   u.in_channel = (int)na.number("in_channel", 2);
   u.out_channel = (int)na.number("out_channel", 1);
   u.inner = (int)na.number("inner_channel", 32);
   u.groups = (int)na.number("norm_groups", 32);
-  u.mults = na.ints("channel_mults", {1, 2, 3, 4, 5});
+  u.mults = na.ints("channel_mults", modified ? std::vector<int>{1, 2, 4, 8, 8} : std::vector<int>{1, 2, 3, 4, 5});
   u.res_blocks = (int)na.number("res_blocks", 3);
   u.dropout = na.number("dropout", 0.0);
   u.seg = (int)na.number("segment_len", 128);
@@ -44,7 +46,8 @@ static int unet_configure(const Json& cfg, const Json& na, bool tst, UNetCfg& u,
   if (u.inner > 128 || u.inner % 32) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "inner_channel %d (multiples of 32 up to 128)", u.inner);
   if (Ns <= u.seg || (Ns - u.seg) % u.stride) FAIL(SDDM_ERR_SHAPE, "num_samples %d: (n - %d) %% %d != 0 (UNetModified2.py:13)", Ns, u.seg, u.stride);
   const int F = (Ns - u.seg) / u.stride + 1;
-  const int div = 1 << (int)u.mults.size();
+  if (modified && u.mults.empty()) FAIL(SDDM_ERR_INVALID_ARG, "channel_mults: at least one level");
+  const int div = modified ? 1 << ((int)u.mults.size() - 1) : 1 << (int)u.mults.size();
   if (F % div || u.seg % div) FAIL(SDDM_ERR_SHAPE, "n_frames %d and segment_len %d must be multiples of %d", F, u.seg, div);
   if (u.seg % u.stride) FAIL(SDDM_ERR_NOT_IMPLEMENTED, "segment_len %% segment_stride != 0");
   if (tst) {   // everything the plan or the Dual_Transformer kernel would refuse later is refused here
@@ -68,6 +71,26 @@ static int unet_configure(const Json& cfg, const Json& na, bool tst, UNetCfg& u,
     if (tok > kTstMaxTokens)
       FAIL(SDDM_ERR_NOT_IMPLEMENTED, "num_samples %d: the bottom level has %d x %d = %d tokens, the Dual_Transformer kernel holds %d",
            Ns, F / div, u.seg / div, tok, kTstMaxTokens);
+  }
+  if (modified) {   // everything the plan or the attention kernels would refuse later is refused here
+    // attn_layer: the reference tests `ind in attn_layer`, so an int (the class default `(4)`) is a TypeError there
+    if (na.at("attn_layer").kind != Json::ARR) FAIL(SDDM_ERR_INVALID_ARG, "attn_layer must be a list of levels (UNetModified.py:238: `ind in attn_layer`)");
+    u.attn = na.ints("attn_layer", {});
+    if (na.has("with_noise_level_emb") && na.number("with_noise_level_emb", 1) == 0)
+      FAIL(SDDM_ERR_NOT_IMPLEMENTED, "with_noise_level_emb=False (the reference fails in nn.Linear(None, ...), UNetModified.py:67)");
+    u.mid_tst = 0;
+    if (u.res_blocks < 0) FAIL(SDDM_ERR_INVALID_ARG, "res_blocks %d", u.res_blocks);
+    if (u.inner != 32 || 512 % u.seg)
+      FAIL(SDDM_ERR_NOT_IMPLEMENTED, "inner_channel %d / segment_len %d: conv_in needs 32 and a divisor of 512", u.inner, u.seg);
+    if (u.groups < 1 || 256 % u.groups)
+      FAIL(SDDM_ERR_NOT_IMPLEMENTED, "norm_groups %d: the GroupNorm finalize needs a divisor of 256", u.groups);
+    for (int m : u.mults)
+      if (m < 1 || (u.inner * m) % u.groups)
+        FAIL(SDDM_ERR_NOT_IMPLEMENTED, "channel_mults / norm_groups: %d channels in groups of %d", u.inner * m, u.groups);
+    for (const auto& L : unet_layers(u, nullptr, nullptr, nullptr))
+      if (!L.attn.empty() && L.cout > kAttnMaxC)
+        FAIL(SDDM_ERR_NOT_IMPLEMENTED, "channel_mults / attn_layer: %s has %d channels, the self-attention kernels hold %d",
+             L.attn.c_str(), L.cout, kAttnMaxC);
   }
   *num_samples = Ns;
   return SDDM_OK;
@@ -97,6 +120,13 @@ static std::map<std::string, std::vector<int64_t>> unet_param_shapes(const UNetC
       if (L.cin != L.cout) {
         s[n + ".res_conv.weight"] = {L.cout, L.cin, 1, 1};
         s[n + ".res_conv.bias"] = {L.cout};
+      }
+      if (!L.attn.empty()) {   // SelfAttention (UNetModified.py:146-148): the qkv conv has no bias
+        s[L.attn + ".norm.weight"] = {L.cout};
+        s[L.attn + ".norm.bias"] = {L.cout};
+        s[L.attn + ".qkv.weight"] = {3 * (int64_t)L.cout, L.cout, 1, 1};
+        s[L.attn + ".out.weight"] = {L.cout, L.cout, 1, 1};
+        s[L.attn + ".out.bias"] = {L.cout};
       }
     } else if (L.kind == 2 || L.kind == 3) {
       s[n + ".conv.weight"] = {L.cout, L.cin, 3, 3};
@@ -254,6 +284,15 @@ int UNetState::upload_weights(sddm_ctx* c) {
       pb.insert(pb.end(), fb.begin(), fb.end());
       temb_off[n] = sc;
       sc += L.cout;
+      if (!L.attn.empty()) {   // the two 1x1 convs as MFMA A fragments (store_frags), the rest fp32
+        const std::string& an = L.attn;
+        const int C = L.cout;
+        pk.f32(an + ".norm.gamma", P(an + ".norm.weight").data);
+        pk.f32(an + ".norm.beta", P(an + ".norm.bias").data);
+        store_frags(pk.raw(an + ".qkv_f", (size_t)3 * C * C * es), 0, P(an + ".qkv.weight").data.data(), 3 * C, C, dt);
+        store_frags(pk.raw(an + ".out_f", (size_t)C * C * es), 0, P(an + ".out.weight").data.data(), C, C, dt);
+        pk.f32(an + ".out.b", P(an + ".out.bias").data);
+      }
     } else if (L.kind == 2 || L.kind == 3) {
       add_conv(n + ".w", P(n + ".conv.weight"), 9);
       pk.f32(n + ".b", P(n + ".conv.bias").data);
@@ -278,6 +317,9 @@ int UNetState::upload_weights(sddm_ctx* c) {
     for (int k = 0; k < half; ++k) {
       const float e = (-(float)k * 4.0f) / (float)half;
       ev[k] = 1e4f * std::pow(10.0f, e);
+      // UNetModified.py:52-56: exp(-ln(1e4) * k / half), no 1e4 factor (the kernel multiplies by the level
+      // and takes sin, then cos, as for the others)
+      if (u.modified) ev[k] = std::exp((float)(-std::log(1e4)) * ((float)k / (float)half));
     }
     pk.f32("emb_vec", ev);
   }
@@ -296,7 +338,7 @@ EmbedArgs UNetState::embed_args(const sddm_ctx* c) const {
   e.w1 = wf("mlp.w1"); e.b1 = wf("mlp.b1");
   e.w2 = wf("mlp.w2"); e.b2 = wf("mlp.b2");
   e.pw = wf("proj.w"); e.pb = wf("proj.b");
-  e.SC = SC; e.no_final_swish = u.mid_tst;
+  e.SC = SC; e.no_final_swish = u.mid_tst || u.modified;
   return e;
 }
 
@@ -321,6 +363,7 @@ static hipError_t launch_conv(const ConvLaunch& p, int flags, hipStream_t s) {
   if (flags & 2) x.gamma = nullptr;
   if (flags & 4) x.res_mode = 0;
   if (flags) x.dbg = flags;
+  if (ch.wide) return launch_conv_wide(p.dt, p.s2, x, p.B, s);
   if (ch.strip) return launch_conv_strip(p.dt, ch.nblk, ch.mpi, ch.SR, x, p.B, s);
   if (ch.tile >= 0) return launch_conv_tile(p.dt, ch.tile, p.s2, x, p.B, s);
   x.deep_zin = deep_zin(x, p.B, dtype_size(p.dt), p.net->plan.knobs.deep_zin); x.deep_nw = ch.nw; x.deep_nb = ch.nb;
@@ -415,7 +458,7 @@ struct LaneBuilder {
     if (a.stamps) {
       SDDM_HIP_CHECK(hipMemset(a.stamps, 0, kStampBytes));
       if (const char* f = std::getenv("SDDM_STAMPS_DBG")) a.dbg = std::atoi(f);   // timing ablations
-      int nb = ch.nb;
+      int nb = ch.nb;   // (conv_wide: 32, as planned)
       if (ch.tile >= 0) { const TileCfg tc = conv_tile_cfg(ch.tile); nb = tc.wco * tc.fc * 16; }
       c->stamp_blocks = ch.strip ? (int64_t)(a.Ho / ch.SR) * B * ((a.Cout + ch.nblk - 1) / ch.nblk)
                                  : (int64_t)a.n_tiles * B * (a.Cout / nb);
@@ -484,6 +527,31 @@ struct LaneBuilder {
     const std::string kn = tname("concat_kernel");
     const int dtv = dt, Bv = B;
     L.ops.push_back({4, bytes, 0.0, [a, dtv, Bv](hipStream_t s, int) { return launch_concat(dtv, a, Bv, s); }, st.w, kn, kn});
+    return SDDM_OK;
+  }
+
+  // SelfAttention: attn_qkv into the scratch tensor, then attn_core (self_attention.hip)
+  int add_attention(const Step& st) {
+    const Tensor src = TT(st.srcA), o = TT(st.out), qkv = TT(st.scratch), ga = TT(plan.gns[st.gn].a);
+    const int C = src.C, P = src.H * src.W;
+    if (C % 32 || C > kAttnMaxC || C % u.groups || 256 % u.groups)
+      FAIL(SDDM_ERR_NOT_IMPLEMENTED, "%s: %d channels in %d groups (multiples of 32 up to %d)", st.w.c_str(), C, u.groups, kAttnMaxC);
+    if (attn_core_lds_bytes(dt, C) > (size_t)kLdsBytes || attn_qkv_lds_bytes(dt, C) > (size_t)kLdsBytes)
+      FAIL(SDDM_ERR_STATE, "%s: LDS", st.w.c_str());
+    AttnArgs a{};
+    a.x = src.p; a.gst = ga.stats; a.gtiles = ga.tiles; a.gntile = ga.n_tile;
+    a.gamma = WF(st.w + ".norm.gamma"); a.beta = WF(st.w + ".norm.beta"); a.groups = u.groups; a.eps = 1e-5f;
+    a.wqkv_f = WV(st.w + ".qkv_f"); a.qkv = qkv.p; a.wout_f = WV(st.w + ".out_f"); a.bout = WF(st.w + ".out.b");
+    a.out = o.p; a.stats = o.stats; a.P = P; a.C = C; a.QT = o.n_tile;
+    a.scale_log2 = (float)(1.4426950408889634 / std::sqrt((double)C));
+    if (o.tiles * o.n_tile != P || o.n_tile != attn_query_tile(P)) FAIL(SDDM_ERR_STATE, "tile mismatch for %s", st.w.c_str());
+    const double bq = (double)B * P * C * es * 4 + 3.0 * C * C * es, fq = 2.0 * B * P * 3.0 * C * C;
+    const double bc = (double)B * P * C * es * (3.0 * ((P + o.n_tile - 1) / o.n_tile) + 2) + (double)C * C * es;
+    const double fc = 4.0 * B * (double)P * P * C + 2.0 * B * P * (double)C * C;
+    const int dtv = dt, Bv = B;
+    const std::string kq = tname("attn_qkv_kernel"), kc = tname("attn_core_kernel", ("," + std::to_string(C / 32) + ">").c_str());
+    L.ops.push_back({4, bq, fq, [a, dtv, Bv](hipStream_t s, int) { return launch_attn_qkv(dtv, a, Bv, s); }, st.w + "[qkv]", kq, kq});
+    L.ops.push_back({4, bc, fc, [a, dtv, Bv](hipStream_t s, int) { return launch_attn_core(dtv, a, Bv, s); }, st.w + "[attention]", kc, kc});
     return SDDM_OK;
   }
 
@@ -568,6 +636,7 @@ int UNetState::build_lane(sddm_ctx* c, Lane& L) {
     else if (st.type == ST_CONV) TRY(b.add_conv(st));
     else if (st.type == ST_CAT) TRY(b.add_concat(st));
     else if (st.type == ST_TST) TRY(b.add_dual_transformer(st));
+    else if (st.type == ST_ATTN) TRY(b.add_attention(st));
     else if (st.type == ST_CONVIN) TRY(b.add_conv_in(st));
     else TRY(b.add_final(st));
   }

@@ -15,9 +15,15 @@ number of frames).  TSTNN (config_tstnn.json) frames at 512 / 256: a depth-4 den
 width, a strided conv to half of it, the block again (``model.tstnn.Dual_Transformer``: single-slope
 PReLUs, the output PReLU before its conv, four layers over 63 frames of 256 positions), a gated mask
 (tanh x sigmoid -> conv -> ReLU) on the encoder's output, a second dense block and a sub-pixel conv back;
-it ignores the noise level.  The reference's SNR-estimator networks are not built."""
+it ignores the noise level.  UNetModified (config_unetmodified.json) is the SR3-style U-Net UNetModified2
+was derived from: spatial self-attention (``model.UNetModified.SelfAttention``: GroupNorm, 1x1 qkv conv,
+one-head softmax attention over all positions of the level, 1x1 out conv, residual; also a module of its
+own) behind the ResnetBlocks of the levels in ``attn_layer`` and behind the first ``mid`` block, no
+Downsample after the last level and ``res_blocks + 1`` decoder blocks per level.  The reference's
+SNR-estimator networks are not built."""
 from .CAUNet import CAUNet  # noqa: F401
 from .tstnn import TSTNN  # noqa: F401
+from .UNetModified import SelfAttention, UNetModified  # noqa: F401
 from .UNetModified2 import UNetModified2  # noqa: F401
 from .UNetTST import Dual_Transformer, UNetTST  # noqa: F401
 from .diffwave import DiffWave  # noqa: F401

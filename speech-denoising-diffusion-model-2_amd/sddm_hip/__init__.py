@@ -24,7 +24,7 @@ TABLE_NAMES = ("betas", "alphas", "alpha_bar", "sqrt_alpha_bar", "predicted_nois
                "sqrt_delta_estimated")
 EXPORTS = ("sddm_abi_version", "sddm_last_error", "sddm_create", "sddm_destroy", "sddm_configure",
            "sddm_load_param", "sddm_missing_params", "sddm_sample", "sddm_sample_noise", "sddm_sample_continuous",
-           "sddm_network_forward", "sddm_dual_transformer",
+           "sddm_network_forward", "sddm_dual_transformer", "sddm_self_attention",
            "sddm_transition", "sddm_q_sample", "sddm_log_spectrogram", "sddm_set_conv_tuning", "sddm_initial_state", "sddm_schedule", "sddm_unet_plan", "sddm_profile_enable",
            "sddm_profile_read", "sddm_profile_ops")
 
@@ -53,6 +53,7 @@ def lib():
         L.sddm_sample_continuous.argtypes = [vp, vp, i64, i64, u64, i64, vp, vp, c_int, vp]
         L.sddm_network_forward.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp]
         L.sddm_dual_transformer.argtypes = [vp, vp, i64, i64, i64, vp, vp]
+        L.sddm_self_attention.argtypes = [vp, ctypes.c_char_p, vp, i64, i64, i64, vp, vp]
         L.sddm_transition.argtypes = [vp, c_int, vp, vp, vp, c_int, i64, i64, u64, i64, vp, vp]
         L.sddm_q_sample.argtypes = [vp, c_int, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp]
         L.sddm_log_spectrogram.argtypes = [vp, i64, i64, c_int, c_int, vp, vp, c_int, vp, vp]
@@ -99,7 +100,7 @@ def schedule(schedule="linear", n_timestep=1000, linear_start=1e-4, linear_end=2
 
 
 def unet_plan(cfg, tuning_text=None, dtype="bfloat16"):
-    """The plan of one UNetModified2 / UNetTST step (host computation in the library, no GPU needed):
+    """The plan of one UNetModified2 / UNetTST / UNetModified step (host computation in the library, no GPU needed):
     a list with one dict per step in launch order; conv steps carry the kernel family, the geometry
     and the kernel choice (sddm_unet_plan).  cfg: a config dict as Context takes it (its "network",
     "num_samples" and "lane_rows" are read); tuning_text: the text of a tuning file, or None."""
@@ -111,9 +112,11 @@ def unet_plan(cfg, tuning_text=None, dtype="bfloat16"):
 
 def planned_kernel(step):
     """A conv step of unet_plan in the tuning table's vocabulary: "strip" | "tile:<cfg>" |
-    "deep:<mt>:<nw>:<nb>" | "chain"."""
+    "deep:<mt>:<nw>:<nb>" | "chain"; "wide:<pixels>" is the K-chunked kernel of the layers none of those
+    holds (no table can ask for it)."""
     k = step["kernel"]
-    return {"tile": f"tile:{step['tile']}", "deep": f"deep:{step['mt']}:{step['nw']}:{step['nb']}"}.get(k, k)
+    return {"tile": f"tile:{step['tile']}", "deep": f"deep:{step['mt']}:{step['nw']}:{step['nb']}",
+            "wide": f"wide:{step['mt']}"}.get(k, k)
 
 
 def _ptr(t):
@@ -206,6 +209,12 @@ class Context:
         import torch
         B, _, dim2, dim1 = x.shape
         check(lib().sddm_dual_transformer(self._h, _ptr(x), B, dim2, dim1, _ptr(out), _stream(torch, x.device)))
+
+    def self_attention(self, layer, x, out):
+        """sddm_self_attention: x, out [B, C, H, W] fp32 on the device, layer e.g. "mid.0.attn" (a UNetModified context)."""
+        import torch
+        B, _, H, W = x.shape
+        check(lib().sddm_self_attention(self._h, layer.encode(), _ptr(x), B, H, W, _ptr(out), _stream(torch, x.device)))
 
     def transition(self, mode, x_t, eps, cond, t, out, seed, row_offset=0):
         import torch

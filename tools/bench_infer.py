@@ -4,7 +4,7 @@
                                 [--dtypes bfloat16,float16,float32] [--log profiles/NAME.log]
                                 [--no-kernels] [--no-unet]
 
-NAME is a key of NETWORKS: Waveunet, Waveunet2, Waveunet3, UNetTST, CAUNet, TSTNN or DenoiseWaveGrad; the
+NAME is a key of NETWORKS: Waveunet, Waveunet2, Waveunet3, UNetTST, UNetModified, CAUNet, TSTNN or DenoiseWaveGrad; the
 table gives the config file and the default batch and samples.  Cases: B x N samples in every dtype,
 `steps` reverse steps of the config's schedule (linear, 1e-6 .. 0.01).  Each case is one warm-up call
 (context, weight upload, workspace, code objects, plan and graph capture where the runtime has them),
@@ -24,6 +24,8 @@ launches_per_step restates the library's launch sequence, at any N:
              2 + 10 * 4, gate 1, final 1, transition 1
   UNetTST    counted: a further profiled call (per-launch events, no graphs) gives the ops of one lane's
              step, and transformer_share, the Dual_Transformer op's part of the summed op times
+  UNetModified  counted the same way; attention_share is the part of the SelfAttention launches (attn_qkv and
+             attn_core per attention layer) in the summed op times
 
 CAUNet and TSTNN: unless --no-kernels, one further call of 5 steps runs under torch.profiler and
 kernel_share gives every kernel family's part of the summed kernel time of that call (template
@@ -67,6 +69,8 @@ NETWORKS = {
     "Waveunet3": {"config": "config_waveunet3.json", "batch": 16, "samples": 16384, "num_samples": False,
                   "launches": 1 + 1 + 27 + 27 + 6 * 3 + 1 + 1},
     "UNetTST": {"config": "config_unettst.json", "batch": 16, "samples": 16448, "num_samples": True, "launches": "ops"},
+    "UNetModified": {"config": "config_unetmodified.json", "batch": 16, "samples": 16448, "num_samples": True,
+                     "launches": "ops"},
     "CAUNet": {"config": "config_caunet.json", "batch": 16, "samples": 16448, "num_samples": True,
                "launches": lambda a: 1 + 1 + 8 * 4 + 2 + 10 * a["n_TSTB"] + 1 + 1,
                "transformer": lambda a, N: (a["n_TSTB"], (N - 128) // 64 + 1, 8)},
@@ -153,7 +157,8 @@ def kernel_shares(torch, spec, network, dtype, B, N, net_args):
 
 
 def profiled_ops(torch, model, cond, res):
-    """UNetTST and its UNetModified2 companion: the ops of one lane's step and the block's share of them."""
+    """UNetTST, its UNetModified2 companion and UNetModified: the ops of one lane's step and the share of the
+    Dual_Transformer or of the SelfAttention launches in them."""
     ctx = model._context(cond.device)
     ctx.profile(True)
     model.infer(cond, seed=1)
@@ -167,6 +172,11 @@ def profiled_ops(torch, model, cond, res):
         res["transformer_launches_per_step"] = len(tst)
         res["transformer_ms"] = sum(o["avg_ms"] for o in tst)
         res["transformer_share"] = sum(o["avg_ms"] * o["launches"] for o in tst) / total if total else 0.0
+    attn = [o for o in ops if ".attn[" in o["name"]]
+    if attn:
+        res["attention_launches_per_step"] = len(attn)
+        res["attention_ms"] = sum(o["avg_ms"] for o in attn)
+        res["attention_share"] = sum(o["avg_ms"] * o["launches"] for o in attn) / total if total else 0.0
 
 
 def run_case(torch, spec, network, dtype, B, N, steps, reps, kernels):
